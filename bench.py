@@ -14,11 +14,24 @@ nreduce = 128Mi fp32, at 1/2/4/8 GPUs (one PE per GPU).
   value = sum over PEs of nreduce*sizeof(T) bytes reduced per step / step time, GiB/s.
 
 One JSON line on rank 0's stdout.  `roofline` is the dominant kernel's algorithmic
-HBM bytes per launch / its HIP-event-timed mean duration; `cpu_baseline` is the CPU
-restatement of reduce_local (oracle/sos_oracle.c, gcc -O2, one core) on a bounded
-sample of the same workload.
+HBM bytes per launch / its HIP-event-timed mean duration.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--sweep]
+A plain N = 1 run does only what the headline needs: set up, warm up, time the K steps,
+write --dump-outputs if asked, print the line.  --full adds every other leg to the line
+(each can be switched off again with its --no-* option): the per-launch kernel median,
+the torch-allocator operand pair, the fold / prefix kernels, the PMC traffic passes, the
+host-resident leg, the 1Mi..256Mi size curve and `cpu_baseline`, the CPU restatement of
+reduce_local (oracle/sos_oracle.c, gcc -O2, one core) on a bounded sample of the same
+workload.
+
+--dump-outputs DIR (N = 1) writes DIR/inout.npy: the combine's inout operand as the last
+timed step left it, in float32 (float64 for every type but float / complexf); an output
+above 64 MB is cut to a fixed, seeded sample of blocks (dump_outputs).  The operands are
+the counter-hash fill of SEED, so the same arguments give the same file.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+       python bench.py --full [--no-cpu] [--no-pmc] ...   (every leg)
+       python bench.py --sweep
        torchrun --nproc-per-node N bench.py --gpus N   (N > 1)
        python bench.py --gpus N   (N > 1, no launcher: bench.py starts the N rank
                                    processes itself and prints rank 0's line)
@@ -52,6 +65,12 @@ def parse():
     p.add_argument("--dtype", default="float")
     p.add_argument("--op", default="sum")
     p.add_argument("--alg", default=os.environ.get("SHMEM_REDUCE_ALGORITHM", "auto"))
+    p.add_argument("--full", action="store_true",
+                   help="N = 1: also run every leg beside the headline (kernel median, torch "
+                        "buffers, fold / prefix kernels, PMC, host-resident, size curve, CPU "
+                        "baseline); the --no-* options below switch single legs off again")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="N = 1: write the last timed step's inout operand to DIR/inout.npy")
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--no-pmc", action="store_true")
@@ -172,6 +191,53 @@ def time_combine(args, torch, heap):
     return e0.elapsed_time(e1) / args.steps, dist_b
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: the most it writes
+DUMP_BLOCK = 1 << 16           # scalars per sampled block
+DUMP_BLOCKS = 96               # sampled blocks of an output above DUMP_MAX_BYTES
+
+
+def dump_blocks(count, itemsize):
+    """(starts, block length) of the scalars --dump-outputs keeps of `count` scalars written
+    `itemsize` bytes each: all of them, or the seeded sample dump_outputs describes."""
+    import numpy as np
+    if count * itemsize <= DUMP_MAX_BYTES:
+        return [0], count
+    rng = np.random.default_rng(SEED)
+    drawn = rng.integers(0, count - DUMP_BLOCK, DUMP_BLOCKS - 2)
+    return sorted([0, count - DUMP_BLOCK] + [int(x) for x in drawn]), DUMP_BLOCK
+
+
+def dump_outputs(args, L, dt, ptr):
+    """--dump-outputs: DIR/inout.npy, the `count` scalars at device address `ptr` (the
+    combine's inout after the last timed step) as float32 (float, complexf) or float64
+    (every other type, converted); a complex element is its (re, im) pair.  Where that
+    exceeds DUMP_MAX_BYTES the file holds DUMP_BLOCKS blocks of DUMP_BLOCK consecutive
+    scalars instead, concatenated in ascending order of their starts: the first block, the
+    last, and starts drawn from default_rng(SEED), so the same arguments pick the same
+    scalars in every run and build."""
+    import ctypes
+
+    import numpy as np
+    from oracle.oracle import NP_TYPES  # the numpy view of each datatype (a table only)
+    raw = np.dtype(NP_TYPES[dt])
+    if raw.kind == "c":
+        raw = np.dtype(np.float32 if raw == np.complex64 else np.float64)
+    count = args.n * L.dtype_size(dt) // raw.itemsize
+    out_t = np.dtype(np.float32 if raw == np.float32 else np.float64)
+    starts, blk = dump_blocks(count, out_t.itemsize)
+    host = np.empty(len(starts) * blk, dtype=raw)
+    memcpy = L.lib().hipMemcpy
+    memcpy.restype = ctypes.c_int
+    memcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    for k, s0 in enumerate(starts):
+        rc = memcpy(host[k * blk:].ctypes.data, ptr + s0 * raw.itemsize, blk * raw.itemsize,
+                    2)  # hipMemcpyDeviceToHost
+        if rc != 0:
+            raise RuntimeError(f"--dump-outputs: hipMemcpy D2H failed ({rc})")
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "inout.npy"), host.astype(out_t, copy=False))
+
+
 def run_combine(args, torch):
     stream = torch.cuda.current_stream()
     S = stream.cuda_stream
@@ -213,21 +279,22 @@ def run_combine(args, torch):
     t1 = time.perf_counter()
     mean_kern_s = e0.elapsed_time(e1) / args.steps / 1e3
     step_s = (t1 - t0) / args.steps
-    # per-launch event pairs, after the timed region: the kernel-only median
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-          for _ in range(min(args.steps, 20))]
-    for s_, e_ in ev:
-        s_.record(stream)
-        launch()
-        e_.record(stream)
-    torch.cuda.synchronize()
-    kern_ms = sorted(s_.elapsed_time(e_) for s_, e_ in ev)
+    if args.dump_outputs:  # before anything else launches on inout
+        dump_outputs(args, L, dt, a.ptr)
+    kern_ms = None
+    if args.full:
+        # per-launch event pairs, after the timed region: the kernel-only median
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+              for _ in range(min(args.steps, 20))]
+        for s_, e_ in ev:
+            s_.record(stream)
+            launch()
+            e_.record(stream)
+        torch.cuda.synchronize()
+        kern_ms = sorted(s_.elapsed_time(e_) for s_, e_ in ev)
     dist_ab = b.ptr - a.ptr
     a.free()
     b.free()
-    # the same kernel on a pair from torch's caching allocator (2 MiB-aligned blocks), for
-    # comparison: the placement of a caller's own buffers is the caller's
-    torch_ms, torch_dist = time_combine(args, torch, heap=False)
     payload = args.n * es
     algo_bytes = 3 * payload  # read in, read inout, write inout
     achieved = algo_bytes / mean_kern_s / 1e9
@@ -252,24 +319,30 @@ def run_combine(args, torch):
                      "traffic": None,
                      "kernel": "sos::k_combine3", "algorithmic_bytes_per_launch": algo_bytes,
                      "mean_kernel_ms": round(mean_kern_s * 1e3, 5),
-                     "mean_kernel_ms_how": "HIP-event span of the timed region / steps",
-                     "median_kernel_ms": round(kern_ms[len(kern_ms) // 2], 5),
-                     "median_kernel_ms_how": "per-launch HIP event pairs, after the timed region"},
+                     "mean_kernel_ms_how": "HIP-event span of the timed region / steps"},
         "operands": {"where": "device symmetric heap (shmemx_malloc_device), one PE",
                      "in_minus_inout_bytes": dist_ab,
                      "in_minus_inout_mod_32KiB": dist_ab % 32768,
                      "note": "the heap starts large allocations an odd multiple of 4 KiB apart "
                              "in HBM's 32 KiB channel interleave (DESIGN.md section 3, "
                              "profiles/r4_offset_probe.txt)"},
-        "torch_allocator_buffers": {
-            "mean_kernel_ms": round(torch_ms, 5),
-            "achieved_GBs": round(algo_bytes / (torch_ms / 1e3) / 1e9, 1),
-            "frac": round(algo_bytes / (torch_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
-            "in_minus_inout_bytes": torch_dist,
-            "in_minus_inout_mod_32KiB": torch_dist % 32768,
-            "note": "the same kernel and timing on two torch.empty buffers (the caller's "
-                    "placement, not the heap's): reported, never `value`"},
     }
+    if not args.full:
+        return res
+    res["roofline"].update({
+        "median_kernel_ms": round(kern_ms[len(kern_ms) // 2], 5),
+        "median_kernel_ms_how": "per-launch HIP event pairs, after the timed region"})
+    # the same kernel on a pair from torch's caching allocator (2 MiB-aligned blocks), for
+    # comparison: the placement of a caller's own buffers is the caller's
+    torch_ms, torch_dist = time_combine(args, torch, heap=False)
+    res["torch_allocator_buffers"] = {
+        "mean_kernel_ms": round(torch_ms, 5),
+        "achieved_GBs": round(algo_bytes / (torch_ms / 1e3) / 1e9, 1),
+        "frac": round(algo_bytes / (torch_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+        "in_minus_inout_bytes": torch_dist,
+        "in_minus_inout_mod_32KiB": torch_dist % 32768,
+        "note": "the same kernel and timing on two torch.empty buffers (the caller's "
+                "placement, not the heap's): reported, never `value`"}
     return res
 
 
@@ -812,6 +885,9 @@ def launch_check(torch):
 def main():
     args = parse()
     world_env = os.environ.get("WORLD_SIZE")
+    if args.dump_outputs and (args.gpus > 1 or args.team or args.sweep):
+        log("error: --dump-outputs covers the N = 1 combine only")
+        return 2
     if world_env is None and args.gpus > 1 and not args.child_pmc:
         # no launcher: run the N ranks from here (a line for N GPUs or none at all)
         rc, line = spawn_ranks(args.gpus, sys.argv[1:])
@@ -839,10 +915,11 @@ def main():
     res = run_combine(args, torch)
     if res is None:
         return 0
-    if rank == 0 and not args.no_adjacent:
+    full = rank == 0 and args.full
+    if full and not args.no_adjacent:
         res["fold_kernel"] = multi_stream_kernel(args, torch, "fold")
         res["scan_prefix_kernel"] = multi_stream_kernel(args, torch, "prefix")
-    if rank == 0 and not args.no_pmc:
+    if full and not args.no_pmc:
         traffic, info = pmc_traffic(args, save_dir=args.pmc_save)
         note = ("(2*FETCH_SIZE + WRITE_SIZE)*1024 B per launch, rocprofv3 --pmc (one pass "
                 "per counter), gfx950 FETCH_SIZE halving corrected")
@@ -858,11 +935,11 @@ def main():
                         traffic[kind] / res[key]["algorithmic_bytes_per_launch"], 5)
         else:
             res["roofline"]["traffic_note"] = str(info)
-    if rank == 0 and not args.no_host:
+    if full and not args.no_host:
         res["host_resident"] = host_resident(args, torch)
-    if rank == 0 and not args.no_curve:
+    if full and not args.no_curve:
         res["size_curve"] = size_curve_n1(args, torch, cpu=not args.no_cpu)
-    if rank == 0 and not args.no_cpu:
+    if full and not args.no_cpu:
         res["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(res), flush=True)
     if _SHMEM_UP:

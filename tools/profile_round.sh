@@ -19,9 +19,9 @@ run() {  # name seconds cmd...
 }
 R=$(pwd)
 # 1. the driver's default N=1 line (runs its own PMC passes; raw CSVs kept)
-run bench_n1 600 python3 bench.py --pmc-save "$R/$out/bench_pmc"
+run bench_n1 600 python3 bench.py --full --pmc-save "$R/$out/bench_pmc"
 # 2. kernel trace + stats of the measured kernels only (headline combine, fold, prefix)
-run kernel_stats 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$out/stats" -o stats -- python3 bench.py --no-pmc --no-cpu --no-host --no-curve --steps 50
+run kernel_stats 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$out/stats" -o stats -- python3 bench.py --full --no-pmc --no-cpu --no-host --no-curve --steps 50
 # 3. the fold inside the 8-PE loopback ring (plan-placed scratch slots): stats + PMC
 run loopback_stats 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$out/loopback" -o loopback -- python3 tools/loopback_bench.py --P 8 --n 134217728 --alg ring
 run loopback_fetch 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$R/$out/loopback_fetch" -o fetch -- python3 tools/loopback_bench.py --P 8 --n 134217728 --alg ring --iters 2
