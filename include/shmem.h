@@ -143,4 +143,7 @@ int pshmem_broadcastmem(shmem_team_t team, void *dest, const void *source, size_
 /* ---- the reduction family + typed broadcasts (generated: gen_bindings.py) --- */
 #include "shmem_reductions.h"
 
+/* ---- fcollect, alltoall, alltoalls (generated: gen_bindings.py) ------------- */
+#include "shmem_collects.h"
+
 #endif /* SHMEM_H */

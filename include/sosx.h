@@ -126,6 +126,14 @@ int sosx_combine3(int op, int dtype, void *out, const void *a, const void *b, si
 #define SOSX_PLAN_INSCAN 16
 #define SOSX_PLAN_EXSCAN 17
 #define SOSX_PLAN_BCAST(root, copy_root) (32 + 2 * (root) + ((copy_root) ? 1 : 0))
+/* fcollect: count = the per-PE contribution; alltoall: count = the per-pair block */
+#define SOSX_PLAN_FCOLLECT 18
+#define SOSX_PLAN_ALLTOALL 19
+/* Extents in bytes of the source and target operands of plan `alg` over P PEs (count *
+ * ts for both except fcollect's target and alltoall's operands, P times that).  Returns
+ * SOSX_OK, or SOSX_ERR_ARG for an id that names no plan, P < 1, ts == 0 or an overflow. */
+int sosx_plan_extents(int alg, int P, unsigned long long count, unsigned long long ts,
+                      unsigned long long *src_bytes, unsigned long long *dst_bytes);
 int sosx_fold(int op, int dtype, int order, void *out, const void *const *ins, int nin,
               size_t count, void *stream);
 
@@ -189,6 +197,15 @@ int sosx_memcpy(void *dst, const void *src, size_t bytes, void *stream);
 /* Multi-segment copy in one launch (peer-to-peer transport gathers). */
 int sosx_gather(int nseg, const void *const *srcs, void *const *dsts, const size_t *bytes,
                 void *stream);
+
+/* Strided element copy on device memory, async on `stream`:
+ * dst[k * dst_stride] = src[k * src_stride] for k < count, elements of elem_size
+ * (1, 2, 4, 8 or 16) bytes, strides in elements (>= 1), pointers multiples of elem_size.
+ * The pack and unpack passes of shmem_alltoalls.  Bytes between target elements are never
+ * written.  Arguments are checked before any device work (SOSX_ERR_ARG); count 0 is a
+ * no-op. */
+int sosx_strided_copy(void *dst, ptrdiff_t dst_stride, const void *src, ptrdiff_t src_stride,
+                      size_t elem_size, size_t count, void *stream);
 
 /* p2p transport signalling (internal): store wval[i] to waddr[i] (i < nw) in stream
  * order, then wait until *qaddr[i] >= qval[i] (i < nq); a wait longer than limit_ticks

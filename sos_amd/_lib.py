@@ -31,6 +31,9 @@ ORDER_LINEAR, ORDER_TREE = 0, 1
 ALGS = {"auto": 0, "recdbl": 1, "ring": 2, "rechalving": 3, "recdbl_direct": 4, "recdbl_gather": 5,
         "inscan": 16, "exscan": 17}
 PLAN_INSCAN, PLAN_EXSCAN = 16, 17
+# count = the per-PE contribution (fcollect) / the per-pair block (alltoall)
+PLAN_FCOLLECT, PLAN_ALLTOALL = 18, 19
+ALGS.update({"fcollect": PLAN_FCOLLECT, "alltoall": PLAN_ALLTOALL})
 
 
 def plan_bcast(root, copy_root):
@@ -106,6 +109,10 @@ _SIGS = {
     "sosx_acquire_system": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     "sosx_gather": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
                                _c.POINTER(_c.c_size_t), _c.c_void_p]),
+    "sosx_strided_copy": (_c.c_int, [_c.c_void_p, _c.c_ssize_t, _c.c_void_p, _c.c_ssize_t, _c.c_size_t,
+                                     _c.c_size_t, _c.c_void_p]),
+    "sosx_plan_extents": (_c.c_int, [_c.c_int, _c.c_int, _c.c_ulonglong, _c.c_ulonglong,
+                                     _c.POINTER(_c.c_ulonglong), _c.POINTER(_c.c_ulonglong)]),
 }
 
 
@@ -215,6 +222,22 @@ def count_mismatch(a_ptr, b_ptr, count, elem_size, stream=None):
     check(lib().sosx_count_mismatch(a_ptr, b_ptr, count, elem_size, ctypes.byref(out), stream),
           "sosx_count_mismatch")
     return out.value
+
+
+def strided_copy(dst_ptr, dst_stride, src_ptr, src_stride, elem_size, count, stream=None):
+    """dst[k * dst_stride] = src[k * src_stride], k < count, on device memory
+    (sosx_strided_copy; strides in elements)."""
+    return check(lib().sosx_strided_copy(dst_ptr, dst_stride, src_ptr, src_stride, elem_size, count,
+                                         stream), "sosx_strided_copy")
+
+
+def plan_extents(alg, P, count, ts):
+    """(src_bytes, dst_bytes) of plan `alg` over P PEs (sosx_plan_extents)."""
+    a = ALGS[alg] if isinstance(alg, str) else int(alg)
+    s, d = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+    check(lib().sosx_plan_extents(a, P, count, ts, ctypes.byref(s), ctypes.byref(d)),
+          "sosx_plan_extents")
+    return s.value, d.value
 
 
 def dtype_size(dtype):

@@ -26,6 +26,15 @@ int sos_api_broadcast(shmem_team_t team, void *dest, const void *source, size_t 
 int sos_api_scan(shmem_team_t team, void *dest, const void *source, size_t nelems,
                  size_t type_size, int op, int datatype, int exclusive, const char *fn);
 
+// SHMEM_DEF_FCOLLECT / SHMEM_DEF_ALLTOALL / SHMEM_DEF_ALLTOALLS
+// (src/collectives_c.c4:536-556, :609-629, :687-705)
+int sos_api_fcollect(shmem_team_t team, void *dest, const void *source, size_t nelems,
+                     size_t type_size, const char *fn);
+int sos_api_alltoall(shmem_team_t team, void *dest, const void *source, size_t nelems,
+                     size_t type_size, const char *fn);
+int sos_api_alltoalls(shmem_team_t team, void *dest, const void *source, ptrdiff_t dst,
+                      ptrdiff_t sst, size_t nelems, size_t type_size, const char *fn);
+
 #ifdef __cplusplus
 }
 #endif

@@ -276,10 +276,9 @@ void execute_p2p(const Plan &p, const Team &t, int alg, size_t count, size_t ts,
                  int dt, const char *fn)
 {
     State &s = st();
-    const size_t bytes = count * ts;
     const char *hb = s.sym_stage;
     if (!direct && p.reads_src)
-        hip_check(hipMemcpyAsync(s.sym_stage, source, bytes, hipMemcpyDefault, s.stream), "stage in");
+        hip_check(hipMemcpyAsync(s.sym_stage, source, p.src_bytes, hipMemcpyDefault, s.stream), "stage in");
     char *scr = nullptr;
     size_t scr_off = 0;
     if (p.scratch_bytes && p.scr_sent) {
@@ -296,7 +295,7 @@ void execute_p2p(const Plan &p, const Team &t, int alg, size_t count, size_t ts,
     // p2p_exec returned with the stream drained; a staged result still has to come out
     // (its target may be pageable memory: a full stream synchronisation)
     if (!direct && p.writes_dst) {
-        hip_check(hipMemcpyAsync(target, s.sym_stage, bytes, hipMemcpyDefault, s.stream), "stage out");
+        hip_check(hipMemcpyAsync(target, ddst, p.dst_bytes, hipMemcpyDefault, s.stream), "stage out");
         hip_check(sync_system(s.stream), fn);
     }
     if (g_prof.on) g_prof.collect();
@@ -464,6 +463,11 @@ void execute(int alg, void *target, const void *source, size_t count, size_t ts,
              int op, int dt, const char *fn, bool reduction = false)
 {
     State &s = st();
+    // operand extents: count * ts for both, except fcollect's target and alltoall's operands
+    uint64_t sb64 = 0, db64 = 0;
+    if (sosplan::extents(alg, t.size, count, ts, &sb64, &db64) != SOSX_OK)
+        raise_error("%s: operand size overflows (count %zu, element size %zu, %d PEs)", fn, count, ts, t.size);
+    const size_t src_bytes = (size_t)sb64, dst_bytes = (size_t)db64;
     const size_t bytes = count * ts;
     int rc;
     ncclDataType_t ar_ty = ncclUint8;
@@ -472,21 +476,27 @@ void execute(int alg, void *target, const void *source, size_t count, size_t ts,
     if (!ar && striped_host_ring(alg, target, source, count, ts, t, op, dt, fn)) return;
     if (s.transport == TRANSPORT_P2P) {
         // buffers must live in the IPC-mapped device heap; anything else is staged
-        // through this PE's stage region (in place), whose offset is published
+        // through this PE's stage region, whose offset is published: in place for the
+        // reductions, scans and broadcasts; fcollect and alltoall receive into target
+        // blocks while peers still read the source, so their target is staged behind the
+        // source (every target byte is written: no stage-in of the target)
         const char *hb = s.sym_stage;
-        auto in_heap = [&](const void *p) {
-            return hb && (const char *)p >= hb && (const char *)p + bytes <= hb + s.dev_heap_bytes;
+        auto in_heap = [&](const void *p, size_t n) {
+            return hb && (const char *)p >= hb && (const char *)p + n <= hb + s.dev_heap_bytes;
         };
-        const bool direct = in_heap(source) && in_heap(target);
+        const bool direct = in_heap(source, src_bytes) && in_heap(target, dst_bytes);
+        const bool split = sosplan::is_fcollect(alg) || sosplan::is_alltoall(alg);
+        const size_t doff = split ? (src_bytes + 255) / 256 * 256 : 0;
         const char *dsrc = direct ? (const char *)source : s.sym_stage;
-        char *ddst = direct ? (char *)target : s.sym_stage;
+        char *ddst = direct ? (char *)target : s.sym_stage + doff;
         const unsigned smis = (unsigned)((uintptr_t)dsrc & 15), dmis = (unsigned)((uintptr_t)ddst & 15);
         const Plan &p = cached_plan(alg, t.size, t.my_idx, count, ts, smis, dmis);
         // the staged operand and the scratch the peers read (scan results) must fit the
         // IPC-mapped stage region; the decision depends only on sizes, residency of
         // symmetric addresses and SHMEMX_STAGE_BYTES, so every PE takes the same branch
-        const size_t base = direct ? 0 : (bytes + 255) / 256 * 256;
-        const size_t need = (p.scratch_bytes && p.scr_sent) ? base + p.scratch_bytes : (direct ? 0 : bytes);
+        const size_t staged = direct ? 0 : (split ? doff + dst_bytes : bytes);
+        const size_t base = (staged + 255) / 256 * 256;
+        const size_t need = (p.scratch_bytes && p.scr_sent) ? base + p.scratch_bytes : staged;
         if (need <= s.sym_stage_bytes) {
             execute_p2p(p, t, alg, count, ts, source, target, dsrc, ddst, direct, base, op, dt, fn);
             return;
@@ -506,11 +516,13 @@ void execute(int alg, void *target, const void *source, size_t count, size_t ts,
     const char *dsrc = (const char *)source;
     char *ddst = (char *)target;
     char *stg = nullptr;
-    const size_t half = (bytes + 255) / 256 * 256;
+    const size_t half = (src_bytes + 255) / 256 * 256;
     if (!dev_src || !dev_dst) {
-        stg = (char *)stage(2 * half);
+        stg = (char *)stage(half + (dst_bytes + 255) / 256 * 256);
         if (!dev_src) dsrc = stg;
-        if (!dev_dst) ddst = target == source ? stg : stg + half;
+        // fcollect and alltoall never run in place: blocks arrive while the source is read
+        const bool split = sosplan::is_fcollect(alg) || sosplan::is_alltoall(alg);
+        if (!dev_dst) ddst = target == source && !split ? stg : stg + half;
     }
     if (ar) {
         if (!dev_src) hip_check(hipMemcpyAsync(stg, source, bytes, hipMemcpyHostToDevice, s.stream), "H2D");
@@ -530,13 +542,13 @@ void execute(int alg, void *target, const void *source, size_t count, size_t ts,
     const Plan &p = cached_plan(alg, t.size, t.my_idx, count, ts, (unsigned)((uintptr_t)dsrc & 15),
                                 (unsigned)((uintptr_t)ddst & 15));
     if (!dev_src && p.reads_src)
-        hip_check(hipMemcpyAsync(stg, source, bytes, hipMemcpyHostToDevice, s.stream), "H2D");
+        hip_check(hipMemcpyAsync(stg, source, p.src_bytes, hipMemcpyHostToDevice, s.stream), "H2D");
     Bufs b{dsrc, ddst, p.scratch_bytes ? (char *)scratch(p.scratch_bytes) : nullptr};
     if (g_prof.on) g_prof.ncall++;
     rc = exec_rccl(p, t, b, op, dt, s.stream);
     if (rc) raise_error("%s: %s", fn, status_text(rc));
     if (!dev_dst && p.writes_dst)
-        hip_check(hipMemcpyAsync(target, ddst, bytes, hipMemcpyDeviceToHost, s.stream), "D2H");
+        hip_check(hipMemcpyAsync(target, ddst, p.dst_bytes, hipMemcpyDeviceToHost, s.stream), "D2H");
     hip_check(sync_system(s.stream), fn);
     if (g_prof.on) g_prof.collect();
 }
@@ -783,6 +795,269 @@ int sos_api_scan(shmem_team_t team, void *dest, const void *source, size_t nelem
     return 0;
 }
 
+// ---- fcollect, alltoall, alltoalls (src/collectives.c:1284-1531) ------------------------
+//
+// Checks in SOS's order (src/collectives_c.c4:505-725), with two deliberate deviations
+// (INTEGRATION.md): the symmetric and overlap checks cover the operands' TRUE extents
+// (SOS checks nelems * size only), and every alltoalls form refuses a stride < 1 (SOS's
+// team forms do not check).
+namespace {
+
+// SHMEM_ERR_CHECK_OVERLAP for operands of different extents; complete overlap allowed
+void check_overlap2(const void *dest, size_t db, const void *source, size_t sb, const char *fn)
+{
+    if (dest == source || !db || !sb) return;
+    const char *d = (const char *)dest, *s = (const char *)source;
+    if (d < s + sb && s < d + db)
+        raise_error("%s: Argument \"dest\" [%p..%p) overlaps argument (%p)", fn, (const void *)d,
+                    (const void *)(d + db), (const void *)s);
+}
+
+// SHMEM_ERR_CHECK_POSITIVE (src/shmem_internal.h:198-204)
+void check_positive(ptrdiff_t v, const char *name, const char *fn)
+{
+    if (v <= 0) raise_error("%s: Argument %s must be positive (%ld)", fn, name, (long)v);
+}
+
+Team *checked_team(shmem_team_t team, const char *fn)
+{
+    Team *t = team_from_handle(team);
+    if (!t || !t->valid) raise_error("%s: invalid team", fn);
+    return t;
+}
+
+Team active_set_team(int PE_start, int logPE_stride, int PE_size, const char *fn)
+{
+    const int stride = active_set_stride(PE_start, logPE_stride, PE_size, fn);
+    Team t;
+    t.start = PE_start;
+    t.stride = stride;
+    t.size = PE_size;
+    t.my_idx = (st().my_pe - PE_start) / stride;
+    t.valid = true;
+    return t;
+}
+
+// es * ((n - 1) * stride + 1): the bytes a strided run of n >= 1 elements spans
+size_t strided_extent(size_t n, ptrdiff_t stride, size_t es, const char *fn)
+{
+    const size_t span = checked_bytes(n - 1, (size_t)stride, "nelems", fn);
+    if (span == SIZE_MAX) raise_error("%s: strided extent overflows size_t", fn);
+    return checked_bytes(span + 1, es, "nelems", fn);
+}
+
+void check_team_size(const Team &t, const char *fn)
+{
+    if (t.size > sosplan::PLAN_MAX_PE)
+        raise_error("%s: teams of more than %d PEs are not supported", fn, sosplan::PLAN_MAX_PE);
+}
+
+void local_copy(void *dest, const void *source, size_t bytes, const char *fn)
+{
+    State &s = st();
+    if (dest != source) hip_check(hipMemcpyAsync(dest, source, bytes, hipMemcpyDefault, s.stream), fn);
+    hip_check(sync_system(s.stream), fn);
+}
+
+// The checked part shared by the team and active-set forms.  pSync (active-set forms) is
+// only checked: it holds SHMEM_SYNC_VALUE on entry and is left so.
+void fcollect_checked(const Team &t, void *dest, const void *source, size_t nelems, size_t es,
+                      const long *pSync, const char *fn)
+{
+    const size_t sb = checked_bytes(nelems, es, "nelems", fn);
+    const size_t db = checked_bytes(sb, (size_t)t.size, "nelems", fn);
+    check_symmetric(dest, db, "dest", fn);
+    check_symmetric(source, sb, "source", fn);
+    if (pSync) check_symmetric(pSync, sizeof(long) * SHMEM_COLLECT_SYNC_SIZE, "pSync", fn);
+    check_overlap2(dest, db, source, sb, fn);
+    if (t.my_idx < 0) raise_error("%s: calling PE is not a member of the team", fn);
+    if (nelems == 0) return;  // src/collectives.c:1351
+    if (t.size == 1) return local_copy(dest, source, sb, fn);
+    check_team_size(t, fn);
+    execute(sosplan::PLAN_FCOLLECT, dest, source, nelems, es, t, SOSX_OP_SUM, SOSX_DT_UCHAR, fn);
+}
+
+void alltoall_checked(const Team &t, void *dest, const void *source, size_t nelems, size_t es,
+                      const long *pSync, const char *fn)
+{
+    const size_t B = checked_bytes(nelems, es, "nelems", fn);
+    const size_t bytes = checked_bytes(B, (size_t)t.size, "nelems", fn);
+    check_symmetric(dest, bytes, "dest", fn);
+    check_symmetric(source, bytes, "source", fn);
+    if (pSync) check_symmetric(pSync, sizeof(long) * SHMEM_ALLTOALL_SYNC_SIZE, "pSync", fn);
+    check_overlap2(dest, bytes, source, bytes, fn);
+    if (t.my_idx < 0) raise_error("%s: calling PE is not a member of the team", fn);
+    if (nelems == 0) return;  // src/collectives.c:1459
+    if (t.size == 1) return local_copy(dest, source, bytes, fn);
+    check_team_size(t, fn);
+    execute(sosplan::PLAN_ALLTOALL, dest, source, nelems, es, t, SOSX_OP_SUM, SOSX_DT_UCHAR, fn);
+}
+
+// alltoalls is PLAN_ALLTOALL over packed operands.  The block for peer j starts at
+// source + j*nelems*sst*es with elements sst apart (src/collectives.c:1514-1521) and the
+// block from PE i lands at dest + i*nelems*dst*es (:1489): the whole source is ONE strided
+// run of P*nelems elements, and so is the whole target.  A strided operand is packed
+// (source) or unpacked (target) by sosx_strided_copy when it is device memory and by a
+// host loop when it is host memory (a kernel cannot reach pageable memory); an operand
+// at stride 1 goes to the executor as it is and runs in place where the executor allows.
+// The unpack writes elements only, into the caller's target: the gaps keep their bytes.
+void alltoalls_checked(const Team &t, void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst,
+                       size_t nelems, size_t es, const long *pSync, const char *fn)
+{
+    State &s = st();
+    const size_t N = checked_bytes(nelems, (size_t)t.size, "nelems", fn);
+    const size_t bytes = checked_bytes(N, es, "nelems", fn);
+    if (N) {
+        check_symmetric(dest, strided_extent(N, dst, es, fn), "dest", fn);
+        check_symmetric(source, strided_extent(N, sst, es, fn), "source", fn);
+    }
+    if (pSync) check_symmetric(pSync, sizeof(long) * SHMEM_ALLTOALLS_SYNC_SIZE, "pSync", fn);
+    if (t.my_idx < 0) raise_error("%s: calling PE is not a member of the team", fn);
+    if (nelems == 0) return;  // src/collectives.c:1494
+    check_team_size(t, fn);
+    const bool dev_s = is_device_ptr(source), dev_d = is_device_ptr(dest);
+    const size_t slot = (bytes + 255) / 256 * 256;
+    // device slots for the packed operands: the exchange scratch, which the alltoall
+    // plan itself never uses
+    char *wk = nullptr;
+    if ((sst != 1 && dev_s) || (dst != 1 && dev_d)) wk = (char *)scratch(2 * slot);
+    std::vector<char> hsrc, hdst;
+    const void *psrc = source;
+    if (sst != 1 && dev_s) {
+        int rc = sosx_strided_copy(wk, 1, source, sst, es, N, s.stream);
+        if (rc) raise_error("%s: %s", fn, status_text(rc));
+        psrc = wk;
+    } else if (sst != 1) {
+        hsrc.resize(bytes);
+        const char *sp = (const char *)source;
+        for (size_t k = 0; k < N; ++k) memcpy(&hsrc[k * es], sp + k * (size_t)sst * es, es);
+        psrc = hsrc.data();
+    }
+    const void *packed = psrc;  // where the packed result is (team of one: the packed source)
+    if (t.size > 1) {
+        void *pdst = dest;
+        if (dst != 1 && dev_d) pdst = wk + slot;
+        else if (dst != 1) {
+            hdst.resize(bytes);
+            pdst = hdst.data();
+        }
+        execute(sosplan::PLAN_ALLTOALL, pdst, psrc, nelems, es, t, SOSX_OP_SUM, SOSX_DT_UCHAR, fn);
+        packed = pdst;
+    }
+    if (dst == 1) {
+        if (t.size == 1) local_copy(dest, packed, bytes, fn);
+        else if (psrc == wk) hip_check(sync_system(s.stream), fn);
+        return;
+    }
+    if (dev_d) {
+        if (!is_device_ptr(packed)) {  // team of one, host source
+            hip_check(hipMemcpyAsync(wk + slot, packed, bytes, hipMemcpyHostToDevice, s.stream), fn);
+            packed = wk + slot;
+        }
+        int rc = sosx_strided_copy(dest, dst, packed, 1, es, N, s.stream);
+        if (rc) raise_error("%s: %s", fn, status_text(rc));
+        hip_check(sync_system(s.stream), fn);
+        return;
+    }
+    if (is_device_ptr(packed)) {  // team of one, device source
+        hdst.resize(bytes);
+        hip_check(hipMemcpyAsync(hdst.data(), packed, bytes, hipMemcpyDeviceToHost, s.stream), fn);
+        hip_check(sync_system(s.stream), fn);
+        packed = hdst.data();
+    }
+    char *dp = (char *)dest;
+    for (size_t k = 0; k < N; ++k) memcpy(dp + k * (size_t)dst * es, (const char *)packed + k * es, es);
+}
+
+}  // namespace
+
+int sos_api_fcollect(shmem_team_t team, void *dest, const void *source, size_t nelems,
+                     size_t type_size, const char *fn)
+{
+    check_initialized(fn);
+    fcollect_checked(*checked_team(team, fn), dest, source, nelems, type_size, nullptr, fn);
+    return 0;
+}
+
+int sos_api_alltoall(shmem_team_t team, void *dest, const void *source, size_t nelems,
+                     size_t type_size, const char *fn)
+{
+    check_initialized(fn);
+    alltoall_checked(*checked_team(team, fn), dest, source, nelems, type_size, nullptr, fn);
+    return 0;
+}
+
+int sos_api_alltoalls(shmem_team_t team, void *dest, const void *source, ptrdiff_t dst,
+                      ptrdiff_t sst, size_t nelems, size_t type_size, const char *fn)
+{
+    check_initialized(fn);
+    check_positive(sst, "sst", fn);
+    check_positive(dst, "dst", fn);
+    alltoalls_checked(*checked_team(team, fn), dest, source, dst, sst, nelems, type_size, nullptr, fn);
+    return 0;
+}
+
+int pshmem_fcollectmem(shmem_team_t team, void *dest, const void *source, size_t nelems)
+{
+    return sos_api_fcollect(team, dest, source, nelems, 1, "shmem_fcollectmem");
+}
+
+int pshmem_alltoallmem(shmem_team_t team, void *dest, const void *source, size_t nelems)
+{
+    return sos_api_alltoall(team, dest, source, nelems, 1, "shmem_alltoallmem");
+}
+
+int pshmem_alltoallsmem(shmem_team_t team, void *dest, const void *source, ptrdiff_t dst,
+                        ptrdiff_t sst, size_t nelems)
+{
+    return sos_api_alltoalls(team, dest, source, dst, sst, nelems, 1, "shmem_alltoallsmem");
+}
+
+#define SOS_DEF_ACTIVE_SET_COLLECTS(BITS, ES)                                                      \
+    void pshmem_fcollect##BITS(void *target, const void *source, size_t nlong, int PE_start,       \
+                               int logPE_stride, int PE_size, long *pSync)                         \
+    {                                                                                              \
+        const char *fn = "shmem_fcollect" #BITS;                                                   \
+        check_initialized(fn);                                                                     \
+        const Team t = active_set_team(PE_start, logPE_stride, PE_size, fn);                       \
+        fcollect_checked(t, target, source, nlong, ES, pSync, fn);                                 \
+    }                                                                                              \
+    void pshmem_alltoall##BITS(void *dest, const void *source, size_t nelems, int PE_start,        \
+                               int logPE_stride, int PE_size, long *pSync)                         \
+    {                                                                                              \
+        const char *fn = "shmem_alltoall" #BITS;                                                   \
+        check_initialized(fn);                                                                     \
+        const Team t = active_set_team(PE_start, logPE_stride, PE_size, fn);                       \
+        alltoall_checked(t, dest, source, nelems, ES, pSync, fn);                                  \
+    }                                                                                              \
+    void pshmem_alltoalls##BITS(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst,      \
+                                size_t nelems, int PE_start, int logPE_stride, int PE_size,        \
+                                long *pSync)                                                       \
+    {                                                                                              \
+        const char *fn = "shmem_alltoalls" #BITS;                                                  \
+        check_initialized(fn);                                                                     \
+        check_positive(sst, "sst", fn);                                                            \
+        check_positive(dst, "dst", fn);                                                            \
+        const Team t = active_set_team(PE_start, logPE_stride, PE_size, fn);                       \
+        alltoalls_checked(t, dest, source, dst, sst, nelems, ES, pSync, fn);                       \
+    }                                                                                              \
+    void shmem_fcollect##BITS(void *, const void *, size_t, int, int, int, long *)                 \
+        __attribute__((weak, alias("pshmem_fcollect" #BITS)));                                     \
+    void shmem_alltoall##BITS(void *, const void *, size_t, int, int, int, long *)                 \
+        __attribute__((weak, alias("pshmem_alltoall" #BITS)));                                     \
+    void shmem_alltoalls##BITS(void *, const void *, ptrdiff_t, ptrdiff_t, size_t, int, int, int,  \
+                               long *) __attribute__((weak, alias("pshmem_alltoalls" #BITS)));
+
+SOS_DEF_ACTIVE_SET_COLLECTS(32, 4)
+SOS_DEF_ACTIVE_SET_COLLECTS(64, 8)
+
+int shmem_fcollectmem(shmem_team_t, void *, const void *, size_t)
+    __attribute__((weak, alias("pshmem_fcollectmem")));
+int shmem_alltoallmem(shmem_team_t, void *, const void *, size_t)
+    __attribute__((weak, alias("pshmem_alltoallmem")));
+int shmem_alltoallsmem(shmem_team_t, void *, const void *, ptrdiff_t, ptrdiff_t, size_t)
+    __attribute__((weak, alias("pshmem_alltoallsmem")));
+
 int shmemx_reduce_local(int op, int datatype, size_t count, const void *in, void *inout)
 {
     check_initialized("shmemx_reduce_local");
@@ -840,8 +1115,11 @@ int sosx_loopback_allreduce(int alg, int P, int op, int datatype, void *const *s
                             void *const *dsts, size_t count, void *stream)
 {
     if (P < 1 || P > SOSX_MAX_FOLD || !srcs || !dsts) return SOSX_ERR_ARG;
-    int rc = sosplan::is_bcast(alg) ? (sos_dtype_info(datatype).size ? SOSX_OK : SOSX_ERR_DTYPE)
-                                    : sos_check_op(op, datatype);
+    // broadcast, fcollect and alltoall move bytes: any sized type, no (op, type) rule;
+    // srcs[p] and dsts[p] span the plan's extents (sosx_plan_extents)
+    const bool moves = sosplan::is_bcast(alg) || sosplan::is_fcollect(alg) || sosplan::is_alltoall(alg);
+    int rc = moves ? (sos_dtype_info(datatype).size ? SOSX_OK : SOSX_ERR_DTYPE)
+                   : sos_check_op(op, datatype);
     if (rc) return rc;
     if (sosplan::is_bcast(alg) && ((alg - sosplan::PLAN_BCAST) >> 1) >= P) return SOSX_ERR_ARG;
     const size_t ts = sos_dtype_info(datatype).size;

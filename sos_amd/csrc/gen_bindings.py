@@ -18,7 +18,11 @@ makes their min/max compare signed -- and writes:
                                   src/collectives_c.c4:402-429) and the 52 scans
                                   (src/collectives_c.c4:294-340)
 
-Run: python sos_amd/csrc/gen_bindings.py   (build() runs it; output is committed).
+  include/shmem_collects.h        72 shmem_<T>_{fcollect,alltoall,alltoalls} prototypes, the
+                                  mem and active-set forms, generics and overloads
+  sos_amd/csrc/collects_gen.cpp   their definitions (src/collectives_c.c4:536-707)
+
+Run: python sos_amd/csrc/gen_bindings.py  (build() runs it; output is committed).
 """
 import os
 import sys
@@ -270,6 +274,100 @@ def source():
     return "\n".join(out)
 
 
+# fcollect / alltoall / alltoalls over the RMA table (SHMEM_BIND_C_RMA of SHMEM_DEF_FCOLLECT,
+# SHMEM_DEF_ALLTOALL, SHMEM_DEF_ALLTOALLS: src/collectives_c.c4:536-558, :609-631, :687-707)
+COLLECTS = ("fcollect", "alltoall", "alltoalls")
+_STRIDES = {"fcollect": "", "alltoall": "", "alltoalls": "ptrdiff_t dst, ptrdiff_t sst, "}
+_STRIDE_ARGS = {"fcollect": "", "alltoall": "", "alltoalls": "dst, sst, "}
+
+
+def collect_sig(prefix, st, ct, kind):
+    return (f"int {prefix}shmem_{st}_{kind}(shmem_team_t team, {ct} *dest, const {ct} *source, "
+            f"{_STRIDES[kind]}size_t nelems)")
+
+
+def collect_mem_sig(prefix, kind):
+    return (f"int {prefix}shmem_{kind}mem(shmem_team_t team, void *dest, const void *source, "
+            f"{_STRIDES[kind]}size_t nelems)")
+
+
+def collect_active_sig(prefix, kind, bits):
+    first = "void *target, const void *source, size_t nlong" if kind == "fcollect" else (
+        f"void *dest, const void *source, {_STRIDES[kind]}size_t nelems")
+    return (f"void {prefix}shmem_{kind}{bits}({first}, int PE_start, int logPE_stride, int PE_size, "
+            f"long *pSync)")
+
+
+def collects_header():
+    out = ["/* shmem_collects.h -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.",
+           " *",
+           " * SOS's fcollect, alltoall and alltoalls: the 72 typed team forms",
+           " * shmem_<T>_{fcollect,alltoall,alltoalls} (src/collectives_c.c4:536-707), the",
+           " * three mem forms, the six deprecated active-set forms, the C11 generic selectors",
+           " * and the C++ overloads.  Included from shmem.h. */",
+           "#ifndef SHMEM_COLLECTS_H", "#define SHMEM_COLLECTS_H", "",
+           "#ifdef __cplusplus", 'extern "C" {', "#endif", ""]
+    for kind in COLLECTS:
+        for st, ct in RMA:
+            out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_sig('', st, ct, kind)};")
+        out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_mem_sig('', kind)};")
+        for bits in (32, 64):
+            out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_active_sig('', kind, bits)};")
+        out.append("")
+    out.append("/* profiling interface: pshmem_* are the implementations, shmem_* weak aliases */")
+    for kind in COLLECTS:
+        for st, ct in RMA:
+            out.append(f"{collect_sig('p', st, ct, kind)};")
+        out.append(f"{collect_mem_sig('p', kind)};")
+        for bits in (32, 64):
+            out.append(f"{collect_active_sig('p', kind, bits)};")
+    out += ["", "#ifdef __cplusplus", "}  /* extern \"C\" */", "#endif", ""]
+    out.append("#if defined(__cplusplus)")
+    for kind in COLLECTS:
+        for st, ct in GENERIC_RMA:
+            out.append(f"static inline int shmem_{kind}(shmem_team_t team, {ct} *dest, const {ct} *source, "
+                       f"{_STRIDES[kind]}size_t nelems) {{ return shmem_{st}_{kind}(team, dest, source, "
+                       f"{_STRIDE_ARGS[kind]}nelems); }}")
+    out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
+    out.append("#ifndef SHMEM_C11_TYPE_EVAL_PTR")
+    out.append("#define SHMEM_C11_TYPE_EVAL_PTR(arg) &*(arg)")
+    out.append("#define SHMEM_C11_ARG1(first, ...) SHMEM_C11_ARG1_HELPER(__VA_ARGS__, sentinel)")
+    out.append("#define SHMEM_C11_ARG1_HELPER(second, ...) second")
+    out.append("#endif")
+    for kind in COLLECTS:
+        out += c11_generic(f"shmem_{kind}", [f"        {ct}*: shmem_{st}_{kind}" for st, ct in GENERIC_RMA])
+    out.append("#endif")
+    out += ["", "#endif /* SHMEM_COLLECTS_H */", ""]
+    return "\n".join(out)
+
+
+def collects_source():
+    out = ["// collects_gen.cpp -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.",
+           "//",
+           "// The 72 typed fcollect / alltoall / alltoalls entry points (SHMEM_DEF_FCOLLECT,",
+           "// SHMEM_DEF_ALLTOALL, SHMEM_DEF_ALLTOALLS over SHMEM_BIND_C_RMA,",
+           "// src/collectives_c.c4:536-707): strong pshmem_*, weak shmem_* aliases.",
+           '#include "shmem.h"', '#include "api_internal.h"', "",
+           'extern "C" {', ""]
+    for kind in COLLECTS:
+        for st, ct in RMA:
+            name = f"shmem_{st}_{kind}"
+            out.append(f"{collect_sig('p', st, ct, kind)}")
+            out.append("{")
+            out.append(f"    return sos_api_{kind}(team, dest, source, {_STRIDE_ARGS[kind]}nelems, "
+                       f"sizeof({ct}), \"{name}\");")
+            out.append("}")
+            out.append(f"{collect_sig('', st, ct, kind)} __attribute__((weak, alias(\"p{name}\")));")
+            out.append("")
+    out += ['}  // extern "C"', ""]
+    return "\n".join(out)
+
+
+def collect_symbols():
+    """The generated fcollect / alltoall / alltoalls names (typed forms only)."""
+    return [f"shmem_{st}_{kind}" for kind in COLLECTS for st, ct in RMA]
+
+
 def symbols():
     """All generated public names (used by the ABI test)."""
     return ([f"shmem_{st}_{op}_to_all" for (st, ct, it), op in TO_ALL]
@@ -283,7 +381,9 @@ def main():
     assert len(RMA) == 24 and len(SCANS) == 52, (len(RMA), len(SCANS))
     targets = {os.path.join(ROOT, "include", "shmem_reductions.h"): header(),
                os.path.join(ROOT, "include", "shmemx_scans.h"): scan_header(),
-               os.path.join(ROOT, "sos_amd", "csrc", "reductions_gen.cpp"): source()}
+               os.path.join(ROOT, "sos_amd", "csrc", "reductions_gen.cpp"): source(),
+               os.path.join(ROOT, "include", "shmem_collects.h"): collects_header(),
+               os.path.join(ROOT, "sos_amd", "csrc", "collects_gen.cpp"): collects_source()}
     check = "--check" in sys.argv
     stale = False
     for path, text in targets.items():

@@ -441,7 +441,71 @@ int build_bcast(int root, bool copy_root, int P, int me, uint64_t count, uint64_
     return SOSX_OK;
 }
 
+Local copy_op(int out_buf, uint64_t out_off, int in_buf, uint64_t in_off, uint64_t bytes)
+{
+    Local l;
+    memset(&l, 0, sizeof(l));
+    l.kind = COPY;
+    l.out_buf = out_buf;
+    l.out_off = out_off;
+    l.nin = 1;
+    l.in_buf[0] = in_buf;
+    l.in_off[0] = in_off;
+    l.count = bytes;
+    return l;
+}
+
+// fcollect (src/collectives.c:1284-1446): DST[q*B, (q+1)*B) = SRC of PE q, B = count*ts.
+// Round 0 places the own contribution, round 1 is a direct allgather inside DST: every
+// PE's chunk over its own link to every peer (the shape allgather_round() recognises).
+int build_fcollect(int P, int me, uint64_t B, Plan *plan)
+{
+    if (P > PLAN_MAX_PE) return SOSX_ERR_ARG;
+    Round c;
+    c.ops.push_back(copy_op(DST, (uint64_t)me * B, SRC, 0, B));
+    plan->rounds.push_back(c);
+    if (P == 1) return SOSX_OK;
+    Round ag;
+    for (int k = 1; k < P; ++k) {
+        const int peer = (me + k) % P;
+        ag.xfers.push_back(xf(1, peer, DST, (uint64_t)me * B, B));
+        ag.xfers.push_back(xf(0, peer, DST, (uint64_t)peer * B, B));
+    }
+    plan->rounds.push_back(ag);
+    return SOSX_OK;
+}
+
+// alltoall (src/collectives.c:1449-1480): block q of my source lands as block `me` of PE
+// q's target, B = count*ts bytes per pair.  One round of P-1 sends and receives, then the
+// self block.
+int build_alltoall(int P, int me, uint64_t B, Plan *plan)
+{
+    if (P > PLAN_MAX_PE) return SOSX_ERR_ARG;
+    Round r;
+    for (int k = 1; k < P; ++k) {
+        const int peer = (me + k) % P;
+        r.xfers.push_back(xf(1, peer, SRC, (uint64_t)peer * B, B));
+        r.xfers.push_back(xf(0, peer, DST, (uint64_t)peer * B, B));
+    }
+    r.ops.push_back(copy_op(DST, (uint64_t)me * B, SRC, (uint64_t)me * B, B));
+    plan->rounds.push_back(r);
+    return SOSX_OK;
+}
+
 }  // namespace
+
+int extents(int alg, int P, uint64_t count, uint64_t ts, uint64_t *src_bytes, uint64_t *dst_bytes)
+{
+    const bool known = (alg >= SOSX_ALG_AUTO && alg <= SOSX_ALG_RECDBL_GATHER) || is_scan(alg) ||
+                       is_fcollect(alg) || is_alltoall(alg) || is_bcast(alg);
+    if (!known || P < 1 || ts == 0) return SOSX_ERR_ARG;
+    if (count > UINT64_MAX / ts) return SOSX_ERR_ARG;
+    const uint64_t B = count * ts;
+    if ((is_fcollect(alg) || is_alltoall(alg)) && B > UINT64_MAX / (uint64_t)P) return SOSX_ERR_ARG;
+    if (src_bytes) *src_bytes = is_alltoall(alg) ? (uint64_t)P * B : B;
+    if (dst_bytes) *dst_bytes = (is_fcollect(alg) || is_alltoall(alg)) ? (uint64_t)P * B : B;
+    return SOSX_OK;
+}
 
 // Largest power of two <= P (src/collectives.c:878-882 for P >= 2).
 int pow2_floor(int P)
@@ -477,6 +541,13 @@ int build(int alg, int P, int me, uint64_t count, uint64_t ts, unsigned src_mis,
     out->scratch_bytes = 0;
     out->reads_src = out->writes_dst = true;
     out->scr_sent = false;
+    out->src_bytes = out->dst_bytes = count * ts;
+    if (is_fcollect(alg) || is_alltoall(alg)) {
+        if (extents(alg, P, count, ts, &out->src_bytes, &out->dst_bytes) != SOSX_OK) return SOSX_ERR_ARG;
+        if (count == 0) return SOSX_OK;
+        return is_fcollect(alg) ? build_fcollect(P, me, count * ts, out)
+                                : build_alltoall(P, me, count * ts, out);
+    }
     if (count == 0) return SOSX_OK;
     if (is_bcast(alg))
         return build_bcast((alg - PLAN_BCAST) >> 1, (alg - PLAN_BCAST) & 1, P, me, count, ts, out);
@@ -576,6 +647,17 @@ extern "C" long long sosx_plan_encode(int alg, int P, int me, unsigned long long
     }
     if (out && cap >= w.size()) memcpy(out, w.data(), w.size() * sizeof(long long));
     return (long long)w.size();
+}
+
+extern "C" int sosx_plan_extents(int alg, int P, unsigned long long count, unsigned long long ts,
+                                 unsigned long long *src_bytes, unsigned long long *dst_bytes)
+{
+    uint64_t s = 0, d = 0;
+    const int rc = sosplan::extents(alg, P, count, ts, &s, &d);
+    if (rc) return rc;
+    if (src_bytes) *src_bytes = s;
+    if (dst_bytes) *dst_bytes = d;
+    return SOSX_OK;
 }
 
 extern "C" int sosx_resolve_alg(int alg, unsigned long long bytes, unsigned long long crossover)

@@ -31,6 +31,11 @@
 //                 vector on every link instead of SOS's P-1 sequential atomic puts).
 //   BCAST         root -> all (src/collectives.c:429-485); large payloads as a
 //                 scatter of P-1 chunks to the non-roots + their direct allgather.
+//   FCOLLECT      every PE's contribution in PE order (src/collectives.c:1284-1446): the
+//                 own copy, then one direct allgather inside DST.
+//   ALLTOALL      block q of the source to PE q (src/collectives.c:1449-1480): one direct
+//                 exchange round, then the self block.  alltoalls runs this plan over
+//                 packed operands (collectives.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -52,10 +57,16 @@ enum Kind : int { FOLD = 0, COPY = 1, PREFIX = 2, ZERO = 3 };
 // above the SOSX_ALG_* range.  Broadcast: PLAN_BCAST + 2*root + copy_root.
 constexpr int PLAN_INSCAN = 16;
 constexpr int PLAN_EXSCAN = 17;
+// fcollect (count = per-PE contribution) and alltoall (count = per-pair block): the only
+// plans whose SRC and DST extents differ from count * ts (Plan::src_bytes / dst_bytes).
+constexpr int PLAN_FCOLLECT = 18;
+constexpr int PLAN_ALLTOALL = 19;
 constexpr int PLAN_BCAST = 32;
 constexpr int PLAN_MAX_PE = 64;   // inputs of one local op: SOSX_MAX_FOLD folds, scan prefixes
 inline bool is_scan(int alg) { return alg == PLAN_INSCAN || alg == PLAN_EXSCAN; }
 inline bool is_bcast(int alg) { return alg >= PLAN_BCAST; }
+inline bool is_fcollect(int alg) { return alg == PLAN_FCOLLECT; }
+inline bool is_alltoall(int alg) { return alg == PLAN_ALLTOALL; }
 inline int bcast_alg(int root, bool copy_root) { return PLAN_BCAST + 2 * root + (copy_root ? 1 : 0); }
 
 struct Xfer {
@@ -90,6 +101,8 @@ struct Plan {
     int alg = 0;
     std::vector<Round> rounds;
     uint64_t scratch_bytes = 0;
+    uint64_t src_bytes = 0;    // extent of SRC (count * ts; alltoall: P * count * ts)
+    uint64_t dst_bytes = 0;    // extent of DST (count * ts; fcollect, alltoall: P * count * ts)
     bool reads_src = true;     // false: a broadcast non-root never reads its source
     bool writes_dst = true;    // false: a broadcast root without copy leaves its target
     bool scr_sent = false;     // true: some transfer sends out of SCR (scans)
@@ -103,12 +116,17 @@ void ring_chunk(uint64_t count, int P, int c, uint64_t *n, uint64_t *first);
 
 // Build the plan of team index `me` (0 <= me < P, 2 <= P <= SOSX_MAX_FOLD for the
 // direct reduction schedules, P <= PLAN_MAX_PE for scans).  `alg` is a SOSX_ALG_*
-// (reduction), PLAN_INSCAN / PLAN_EXSCAN (sum scans, SOS src/collectives.c:1111-1209)
+// (reduction), PLAN_INSCAN / PLAN_EXSCAN (sum scans, SOS src/collectives.c:1111-1209),
+// PLAN_FCOLLECT / PLAN_ALLTOALL (P <= PLAN_MAX_PE)
 // or bcast_alg(root, copy_root) (src/collectives.c:429-551 bcast_linear/tree).  src_mis/dst_mis = caller pointer addresses mod 16, so scratch
 // slots can be placed 16-B congruent with the caller's chunks (vector path).
 // Returns SOSX_OK or SOSX_ERR_ARG.
 int build(int alg, int P, int me, uint64_t count, uint64_t ts, unsigned src_mis,
           unsigned dst_mis, Plan *out);
+
+// Extents in bytes of SRC and DST for plan `alg` (what build() records in the plan).
+// SOSX_ERR_ARG: no such plan id, P < 1, ts == 0, or a product that does not fit 64 bits.
+int extents(int alg, int P, uint64_t count, uint64_t ts, uint64_t *src_bytes, uint64_t *dst_bytes);
 
 // Resolve SOSX_ALG_AUTO the way SOS AUTO does without NIC atomics
 // (src/shmem_collectives.h:180-199): recdbl below `crossover` bytes, else ring.

@@ -55,6 +55,22 @@ _RUNTIME = {
                                  _c.c_int, _c.c_void_p]),
     "shmem_broadcast64": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
                                  _c.c_int, _c.c_void_p]),
+    "shmem_fcollectmem": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t]),
+    "shmem_alltoallmem": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t]),
+    "shmem_alltoallsmem": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_ssize_t,
+                                      _c.c_ssize_t, _c.c_size_t]),
+    "shmem_fcollect32": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
+                                _c.c_void_p]),
+    "shmem_fcollect64": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
+                                _c.c_void_p]),
+    "shmem_alltoall32": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
+                                _c.c_void_p]),
+    "shmem_alltoall64": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
+                                _c.c_void_p]),
+    "shmem_alltoalls32": (None, [_c.c_void_p, _c.c_void_p, _c.c_ssize_t, _c.c_ssize_t, _c.c_size_t,
+                                 _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "shmem_alltoalls64": (None, [_c.c_void_p, _c.c_void_p, _c.c_ssize_t, _c.c_ssize_t, _c.c_size_t,
+                                 _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
     "sosx_prof_enable": (None, [_c.c_int]),
     "sosx_prof_get": (None, [_c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                              _c.POINTER(_c.c_long), _c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
@@ -63,6 +79,7 @@ _RUNTIME = {
 _REDUCE_RE = re.compile(r"^shmem_(\w+?)_(and|or|xor|min|max|sum|prod)_(reduce|to_all)$")
 _SCAN_RE = re.compile(r"^shmemx_(\w+?)_sum_(inscan|exscan)$")
 _BCAST_RE = re.compile(r"^shmem_(\w+?)_broadcast$")
+_COLLECT_RE = re.compile(r"^shmem_(\w+?)_(fcollect|alltoalls|alltoall)$")
 _declared = False
 
 
@@ -113,6 +130,15 @@ def __getattr__(name):
         fn = getattr(L, name)
         fn.restype = ctypes.c_int
         fn.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int]
+        return fn
+    m = _COLLECT_RE.match(name)
+    if m and name not in _RUNTIME:
+        # shmem_<T>_fcollect / _alltoall (team, dest, source, nelems) and
+        # shmem_<T>_alltoalls (team, dest, source, dst, sst, nelems)
+        fn = getattr(L, name)
+        fn.restype = ctypes.c_int
+        strides = [_c.c_ssize_t, _c.c_ssize_t] if m.group(2) == "alltoalls" else []
+        fn.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_void_p] + strides + [_c.c_size_t]
         return fn
     if name in _RUNTIME:
         return getattr(L, name)
