@@ -146,4 +146,7 @@ int pshmem_broadcastmem(shmem_team_t team, void *dest, const void *source, size_
 /* ---- fcollect, alltoall, alltoalls (generated: gen_bindings.py) ------------- */
 #include "shmem_collects.h"
 
+/* ---- collect: per-PE lengths (generated: gen_bindings.py) ------------------- */
+#include "shmem_collectv.h"
+
 #endif /* SHMEM_H */

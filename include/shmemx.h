@@ -76,6 +76,10 @@ SHMEM_FUNCTION_ATTRIBUTES int shmemx_set_reduce_algorithm(int alg);
 SHMEM_FUNCTION_ATTRIBUTES int sosx_loopback_allreduce(int alg, int P, int op, int datatype,
                                                       void *const *srcs, void *const *dsts,
                                                       size_t count, void *stream);
+/* The same for shmem_collect: all P collect plans for the byte lengths lens[0..P), P <= 64;
+ * srcs[p] spans lens[p] bytes (may be null when that is 0) and dsts[p] their sum. */
+SHMEM_FUNCTION_ATTRIBUTES int sosx_loopback_collect(int P, void *const *srcs, void *const *dsts,
+                                                    const size_t *lens, void *stream);
 
 #ifdef __cplusplus
 }  /* extern "C" */

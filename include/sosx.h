@@ -129,6 +129,13 @@ int sosx_combine3(int op, int dtype, void *out, const void *a, const void *b, si
 /* fcollect: count = the per-PE contribution; alltoall: count = the per-pair block */
 #define SOSX_PLAN_FCOLLECT 18
 #define SOSX_PLAN_ALLTOALL 19
+/* collect: the plan depends on every PE's byte length, not on a count; it is built and
+ * run through entries of its own (sosx_plan_encode_collect, sosx_loopback_collect) and
+ * has no sosx_plan_extents answer (source = lens[me] bytes, target = their sum). */
+#define SOSX_PLAN_COLLECT 20
+long long sosx_plan_encode_collect(int P, int me, const unsigned long long *lens,
+                                   unsigned long long *src_bytes, unsigned long long *dst_bytes,
+                                   long long *out, unsigned long long cap);
 /* Extents in bytes of the source and target operands of plan `alg` over P PEs (count *
  * ts for both except fcollect's target and alltoall's operands, P times that).  Returns
  * SOSX_OK, or SOSX_ERR_ARG for an id that names no plan, P < 1, ts == 0 or an overflow. */
@@ -299,6 +306,14 @@ void sosx_p2p_flags(unsigned *host_register, unsigned *ipc_open);
 int sosx_small_stage(void *dst, const void *src, size_t bytes, uint64_t *const *words,
                      const uint64_t *vals, int nwords, void *stream);
 
+/* Collect's small path: concatenate np <= 64 segments of any byte lengths (zeros
+ * included) into `out` in one launch; workgroup b stores `seq` into flags[b], b < *nblocks
+ * (flags: np + sum / 16 KiB words of pinned memory).  SOSX_ERR_ARG before any launch for
+ * np outside [1, 64] or a null pointer with a non-zero length. */
+int sosx_small_collect(void *out, const void *const *segs, const size_t *lens, int np,
+                       uint32_t *flags, uint32_t seq, int *nblocks, void *stream);
+/* How many collect calls took the small path (SHMEMX_SMALL_COLLECT=0: none can). */
+long sosx_small_collect_calls(void);
 long sosx_small_path_calls(void);
 long sosx_small_path_device_calls(void);
 /* Limit for device-resident operands on that path: a call takes it when team size *

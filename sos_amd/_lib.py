@@ -34,6 +34,9 @@ PLAN_INSCAN, PLAN_EXSCAN = 16, 17
 # count = the per-PE contribution (fcollect) / the per-pair block (alltoall)
 PLAN_FCOLLECT, PLAN_ALLTOALL = 18, 19
 ALGS.update({"fcollect": PLAN_FCOLLECT, "alltoall": PLAN_ALLTOALL})
+# collect: built from the per-PE byte lengths (shmem.plan_collect, shmem.loopback_collect),
+# so it is no entry of ALGS
+PLAN_COLLECT = 20
 
 
 def plan_bcast(root, copy_root):
@@ -92,6 +95,10 @@ _SIGS = {
     "sosx_build_info": (_c.c_char_p, []),
     "sosx_small_path_calls": (_c.c_long, []),
     "sosx_small_path_device_calls": (_c.c_long, []),
+    "sosx_small_collect": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
+                                      _c.c_int, _c.c_void_p, _c.c_uint32, _c.POINTER(_c.c_int),
+                                      _c.c_void_p]),
+    "sosx_small_collect_calls": (_c.c_long, []),
     "sosx_small_stage": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p,
                                     _c.c_int, _c.c_void_p]),
     "sosx_set_small_device_bytes": (_c.c_size_t, [_c.c_size_t]),

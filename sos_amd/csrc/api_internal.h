@@ -30,6 +30,11 @@ int sos_api_scan(shmem_team_t team, void *dest, const void *source, size_t nelem
 // (src/collectives_c.c4:536-556, :609-629, :687-705)
 int sos_api_fcollect(shmem_team_t team, void *dest, const void *source, size_t nelems,
                      size_t type_size, const char *fn);
+// SHMEM_DEF_COLLECT and shmem_collect32/64 (src/collectives_c.c4:432-503)
+int sos_api_collect(shmem_team_t team, void *dest, const void *source, size_t nelems,
+                    size_t type_size, const char *fn);
+void sos_api_collect_active(void *target, const void *source, size_t nlong, size_t type_size,
+                            int PE_start, int logPE_stride, int PE_size, long *pSync, const char *fn);
 int sos_api_alltoall(shmem_team_t team, void *dest, const void *source, size_t nelems,
                      size_t type_size, const char *fn);
 int sos_api_alltoalls(shmem_team_t team, void *dest, const void *source, ptrdiff_t dst,

@@ -140,7 +140,10 @@ int run_locals(const sosplan::Round &r, const Bufs &b, int op, int dt, hipStream
 // DST: one send of this PE's chunk (bytes B at off0 + me*B) to every other PE and one
 // receive of PE q's chunk at off0 + q*B from every PE q, no local ops?  (The ring and
 // recdbl_direct plans' second round when P divides nreduce.)  Then RCCL's own
-// allgather moves exactly the bytes the send/receive pairs would.
+// allgather moves exactly the bytes the send/receive pairs would.  A collect's uneven
+// round never passes: every transfer must carry the same byte count at owner * bytes, which
+// for a collect holds only when all P lengths are equal (a zero length drops transfers,
+// so the count of 2(P-1) fails first).
 bool allgather_round(const sosplan::Round &r, const Team &t, uint64_t *off0, uint64_t *B)
 {
     const State &s = st();
@@ -243,16 +246,19 @@ bool rccl_allreduce_type(const Team &t, int op, int dt, ncclDataType_t *ty, nccl
 }
 
 // Plan cache: the same call shape every step reuses its plan.
+// A collect's plan is a function of the P byte lengths `lens` as well (empty otherwise).
 const Plan &cached_plan(int alg, int P, int me, uint64_t count, uint64_t ts, unsigned smis,
-                        unsigned dmis)
+                        unsigned dmis, const uint64_t *lens = nullptr)
 {
-    static std::map<std::tuple<int, int, int, uint64_t, uint64_t, unsigned, unsigned>, Plan> cache;
-    auto key = std::make_tuple(alg, P, me, count, ts, smis, dmis);
+    static std::map<std::tuple<int, int, int, uint64_t, uint64_t, unsigned, unsigned,
+                               std::vector<uint64_t>>, Plan> cache;
+    auto key = std::make_tuple(alg, P, me, count, ts, smis, dmis,
+                               lens ? std::vector<uint64_t>(lens, lens + P) : std::vector<uint64_t>());
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
     if (cache.size() > 64) cache.clear();
     Plan p;
-    if (sosplan::build(alg, P, me, count, ts, smis, dmis, &p) != SOSX_OK)
+    if (sosplan::build(alg, P, me, count, ts, smis, dmis, &p, lens) != SOSX_OK)
         raise_error("internal: cannot build reduction plan (alg %d, P %d)", alg, P);
     return cache.emplace(key, std::move(p)).first->second;
 }
@@ -273,11 +279,11 @@ const char *status_text(int rc)
 // others are staged through the stage region; scan scratch follows the staged operand.
 void execute_p2p(const Plan &p, const Team &t, int alg, size_t count, size_t ts, const void *source,
                  void *target, const char *dsrc, char *ddst, bool direct, size_t base, int op,
-                 int dt, const char *fn)
+                 int dt, const char *fn, const uint64_t *lens = nullptr)
 {
     State &s = st();
     const char *hb = s.sym_stage;
-    if (!direct && p.reads_src)
+    if (!direct && p.reads_src && p.src_bytes)
         hip_check(hipMemcpyAsync(s.sym_stage, source, p.src_bytes, hipMemcpyDefault, s.stream), "stage in");
     char *scr = nullptr;
     size_t scr_off = 0;
@@ -290,7 +296,7 @@ void execute_p2p(const Plan &p, const Team &t, int alg, size_t count, size_t ts,
     const unsigned smis = (unsigned)((uintptr_t)dsrc & 15), dmis = (unsigned)((uintptr_t)ddst & 15);
     P2PBufs pb{dsrc, ddst, scr, (size_t)(dsrc - hb), (size_t)(ddst - hb), scr_off, smis, dmis};
     if (g_prof.on) g_prof.ncall++;
-    int rc = p2p_exec(p, t, alg, count, ts, pb, op, dt, s.stream);
+    int rc = p2p_exec(p, t, alg, count, ts, pb, op, dt, s.stream, lens);
     if (rc) raise_error("%s: %s", fn, status_text(rc));
     // p2p_exec returned with the stream drained; a staged result still has to come out
     // (its target may be pageable memory: a full stream synchronisation)
@@ -458,14 +464,23 @@ bool striped_host_ring(int alg, void *target, const void *source, size_t count, 
 
 // Run plan `alg` (a reduction SOSX_ALG_*, a scan or a broadcast, plan.h) for this PE
 // over team t, on the library stream; returns when the call is complete.  `reduction`:
-// the call may take the ncclAllReduce path (rccl_allreduce_type).
+// the call may take the ncclAllReduce path (rccl_allreduce_type).  `lens`: PLAN_COLLECT's P
+// byte lengths (count and ts are not used then).
 void execute(int alg, void *target, const void *source, size_t count, size_t ts, const Team &t,
-             int op, int dt, const char *fn, bool reduction = false)
+             int op, int dt, const char *fn, bool reduction = false, const uint64_t *lens = nullptr)
 {
     State &s = st();
     // operand extents: count * ts for both, except fcollect's target and alltoall's operands
-    uint64_t sb64 = 0, db64 = 0;
-    if (sosplan::extents(alg, t.size, count, ts, &sb64, &db64) != SOSX_OK)
+    // and a collect's own length and the sum of all
+    uint64_t sb64 = 0, db64 = 0, maxlen = 0;
+    const bool collect = sosplan::is_collect(alg);
+    if (collect) {
+        sb64 = lens[t.my_idx];
+        for (int q = 0; q < t.size; ++q) {
+            db64 += lens[q];
+            maxlen = std::max(maxlen, lens[q]);
+        }
+    } else if (sosplan::extents(alg, t.size, count, ts, &sb64, &db64) != SOSX_OK)
         raise_error("%s: operand size overflows (count %zu, element size %zu, %d PEs)", fn, count, ts, t.size);
     const size_t src_bytes = (size_t)sb64, dst_bytes = (size_t)db64;
     const size_t bytes = count * ts;
@@ -485,12 +500,14 @@ void execute(int alg, void *target, const void *source, size_t count, size_t ts,
             return hb && (const char *)p >= hb && (const char *)p + n <= hb + s.dev_heap_bytes;
         };
         const bool direct = in_heap(source, src_bytes) && in_heap(target, dst_bytes);
-        const bool split = sosplan::is_fcollect(alg) || sosplan::is_alltoall(alg);
-        const size_t doff = split ? (src_bytes + 255) / 256 * 256 : 0;
+        // (a collect's target sits behind the LONGEST contribution, so that the fit test
+        // below sees the same size on every PE)
+        const bool split = sosplan::is_fcollect(alg) || sosplan::is_alltoall(alg) || collect;
+        const size_t doff = split ? ((collect ? (size_t)maxlen : src_bytes) + 255) / 256 * 256 : 0;
         const char *dsrc = direct ? (const char *)source : s.sym_stage;
         char *ddst = direct ? (char *)target : s.sym_stage + doff;
         const unsigned smis = (unsigned)((uintptr_t)dsrc & 15), dmis = (unsigned)((uintptr_t)ddst & 15);
-        const Plan &p = cached_plan(alg, t.size, t.my_idx, count, ts, smis, dmis);
+        const Plan &p = cached_plan(alg, t.size, t.my_idx, count, ts, smis, dmis, lens);
         // the staged operand and the scratch the peers read (scan results) must fit the
         // IPC-mapped stage region; the decision depends only on sizes, residency of
         // symmetric addresses and SHMEMX_STAGE_BYTES, so every PE takes the same branch
@@ -498,7 +515,7 @@ void execute(int alg, void *target, const void *source, size_t count, size_t ts,
         const size_t base = (staged + 255) / 256 * 256;
         const size_t need = (p.scratch_bytes && p.scr_sent) ? base + p.scratch_bytes : staged;
         if (need <= s.sym_stage_bytes) {
-            execute_p2p(p, t, alg, count, ts, source, target, dsrc, ddst, direct, base, op, dt, fn);
+            execute_p2p(p, t, alg, count, ts, source, target, dsrc, ddst, direct, base, op, dt, fn, lens);
             return;
         }
         if (!s.comm)
@@ -521,7 +538,7 @@ void execute(int alg, void *target, const void *source, size_t count, size_t ts,
         stg = (char *)stage(half + (dst_bytes + 255) / 256 * 256);
         if (!dev_src) dsrc = stg;
         // fcollect and alltoall never run in place: blocks arrive while the source is read
-        const bool split = sosplan::is_fcollect(alg) || sosplan::is_alltoall(alg);
+        const bool split = sosplan::is_fcollect(alg) || sosplan::is_alltoall(alg) || collect;
         if (!dev_dst) ddst = target == source && !split ? stg : stg + half;
     }
     if (ar) {
@@ -540,8 +557,8 @@ void execute(int alg, void *target, const void *source, size_t count, size_t ts,
         return;
     }
     const Plan &p = cached_plan(alg, t.size, t.my_idx, count, ts, (unsigned)((uintptr_t)dsrc & 15),
-                                (unsigned)((uintptr_t)ddst & 15));
-    if (!dev_src && p.reads_src)
+                                (unsigned)((uintptr_t)ddst & 15), lens);
+    if (!dev_src && p.reads_src && p.src_bytes)
         hip_check(hipMemcpyAsync(stg, source, p.src_bytes, hipMemcpyHostToDevice, s.stream), "H2D");
     Bufs b{dsrc, ddst, p.scratch_bytes ? (char *)scratch(p.scratch_bytes) : nullptr};
     if (g_prof.on) g_prof.ncall++;
@@ -893,6 +910,64 @@ void alltoall_checked(const Team &t, void *dest, const void *source, size_t nele
     execute(sosplan::PLAN_ALLTOALL, dest, source, nelems, es, t, SOSX_OP_SUM, SOSX_DT_UCHAR, fn);
 }
 
+// collect (src/collectives.c:1215-1276): every PE contributes its OWN nelems and the
+// target holds the contributions in PE order.  No PE knows the others' lengths on entry
+// (SOS runs a linear prefix over pSync); here the team first exchanges the byte lengths:
+// in the headers of the small path's slots where the node shared segment exists
+// (small_collect_exchange, which also carries the payloads of small calls), else by an
+// internal PLAN_FCOLLECT of one uint64_t per PE through execute(), on two pinned buffers
+// the library allocates once (State::collect_lens).  Then every PE builds PLAN_COLLECT
+// from the same P lengths.
+void exchange_lengths(const Team &t, uint64_t mine, uint64_t *lens, const char *fn)
+{
+    uint64_t *&buf = st().collect_lens;  // [0]: this PE's length; [1, 1 + PLAN_MAX_PE): everyone's
+    if (!buf)
+        hip_check(hipHostMalloc((void **)&buf, (1 + sosplan::PLAN_MAX_PE) * sizeof(uint64_t), hipHostMallocDefault),
+                  "hipHostMalloc(collect lengths)");
+    buf[0] = mine;
+    execute(sosplan::PLAN_FCOLLECT, buf + 1, buf, 1, sizeof(uint64_t), t, SOSX_OP_SUM, SOSX_DT_UCHAR, fn);
+    memcpy(lens, buf + 1, (size_t)t.size * sizeof(uint64_t));
+}
+
+// The checked part shared by the team and active-set forms, in SOS's order
+// (src/collectives_c.c4:436-441, :468-473).  One deviation: once the
+// lengths are known, the target's TRUE extent -- the sum of the lengths -- is checked for
+// symmetry and for overlap with the source; SOS has written by the time it could know.
+void collect_checked(const Team &t, void *dest, const void *source, size_t nelems, size_t es,
+                     const long *pSync, const char *fn)
+{
+    const size_t sb = checked_bytes(nelems, es, "nelems", fn);
+    check_symmetric(dest, sb, "dest", fn);
+    check_symmetric(source, sb, "source", fn);
+    if (pSync) check_symmetric(pSync, sizeof(long) * SHMEM_COLLECT_SYNC_SIZE, "pSync", fn);
+    check_overlap2(dest, sb, source, sb, fn);
+    if (t.my_idx < 0) raise_error("%s: calling PE is not a member of the team", fn);
+    if (t.size == 1) {  // src/collectives.c:1229-1232
+        if (sb) local_copy(dest, source, sb, fn);
+        return;
+    }
+    check_team_size(t, fn);
+    // nelems == 0 is legal and that PE still takes part: its peers need its length
+    uint64_t lens[sosplan::PLAN_MAX_PE];
+    bool all_payload = false;
+    const bool slots = small_collect_exchange(t, source, sb, lens, &all_payload, fn);
+    if (!slots) exchange_lengths(t, sb, lens, fn);
+    uint64_t sum = 0;
+    for (int q = 0; q < t.size; ++q) {
+        if (lens[q] > (uint64_t)SIZE_MAX - sum)
+            raise_error("%s: the contributions of the %d PEs overflow size_t", fn, t.size);
+        sum += lens[q];
+    }
+    if (sum) {
+        check_symmetric(dest, (size_t)sum, "dest", fn);
+        check_overlap2(dest, (size_t)sum, source, sb, fn);
+    }
+    // every payload attached (a uniform fact of the headers): one kernel writes the target
+    if (slots) small_collect_finish(t, dest, lens, all_payload, fn);
+    if (sum == 0 || (slots && all_payload)) return;  // every PE sees the same lengths
+    execute(sosplan::PLAN_COLLECT, dest, source, 0, 1, t, SOSX_OP_SUM, SOSX_DT_UCHAR, fn, false, lens);
+}
+
 // alltoalls is PLAN_ALLTOALL over packed operands.  The block for peer j starts at
 // source + j*nelems*sst*es with elements sst apart (src/collectives.c:1514-1521) and the
 // block from PE i lands at dest + i*nelems*dst*es (:1489): the whole source is ONE strided
@@ -977,6 +1052,23 @@ int sos_api_fcollect(shmem_team_t team, void *dest, const void *source, size_t n
     check_initialized(fn);
     fcollect_checked(*checked_team(team, fn), dest, source, nelems, type_size, nullptr, fn);
     return 0;
+}
+
+int sos_api_collect(shmem_team_t team, void *dest, const void *source, size_t nelems,
+                    size_t type_size, const char *fn)
+{
+    check_initialized(fn);
+    collect_checked(*checked_team(team, fn), dest, source, nelems, type_size, nullptr, fn);
+    return 0;
+}
+
+void sos_api_collect_active(void *target, const void *source, size_t nlong, size_t type_size,
+                            int PE_start, int logPE_stride, int PE_size, long *pSync, const char *fn)
+{
+    check_initialized(fn);
+    const Team t = active_set_team(PE_start, logPE_stride, PE_size, fn);
+    // pSync is only checked: it holds SHMEM_SYNC_VALUE on entry and is left so
+    collect_checked(t, target, source, nlong, type_size, pSync, fn);
 }
 
 int sos_api_alltoall(shmem_team_t team, void *dest, const void *source, size_t nelems,
@@ -1111,29 +1203,13 @@ void sosx_prof_get(double *fold_ms, double *xfer_ms, long *nfold, long *nxfer, l
 }
 
 // ---- single-GPU loopback team -------------------------------------------------------
-int sosx_loopback_allreduce(int alg, int P, int op, int datatype, void *const *srcs,
-                            void *const *dsts, size_t count, void *stream)
+// Run the P plans over srcs/dsts/scr (scr[p] owned: freed here) with device-to-device
+// copies as the transport, matched FIFO per ordered pair as RCCL matches.
+static int run_loopback(const std::vector<Plan> &plans, void *const *srcs, void *const *dsts,
+                        std::vector<void *> &scr, int op, int datatype, hipStream_t sm)
 {
-    if (P < 1 || P > SOSX_MAX_FOLD || !srcs || !dsts) return SOSX_ERR_ARG;
-    // broadcast, fcollect and alltoall move bytes: any sized type, no (op, type) rule;
-    // srcs[p] and dsts[p] span the plan's extents (sosx_plan_extents)
-    const bool moves = sosplan::is_bcast(alg) || sosplan::is_fcollect(alg) || sosplan::is_alltoall(alg);
-    int rc = moves ? (sos_dtype_info(datatype).size ? SOSX_OK : SOSX_ERR_DTYPE)
-                   : sos_check_op(op, datatype);
-    if (rc) return rc;
-    if (sosplan::is_bcast(alg) && ((alg - sosplan::PLAN_BCAST) >> 1) >= P) return SOSX_ERR_ARG;
-    const size_t ts = sos_dtype_info(datatype).size;
-    hipStream_t sm = (hipStream_t)stream;
-    const int a = sosplan::resolve_alg(alg, count * ts, 16384);
-    std::vector<Plan> plans(P);
-    std::vector<void *> scr(P, nullptr);
-    for (int p = 0; p < P; ++p) {
-        rc = sosplan::build(a, P, p, count, ts, (unsigned)((uintptr_t)srcs[p] & 15),
-                            (unsigned)((uintptr_t)dsts[p] & 15), &plans[p]);
-        if (rc) return rc;
-        if (plans[p].scratch_bytes && hipMalloc(&scr[p], plans[p].scratch_bytes) != hipSuccess)
-            return SOSX_ERR_HIP;
-    }
+    const int P = (int)plans.size();
+    int rc;
     struct Send { const char *ptr; uint64_t bytes; int from; };
     std::map<std::pair<int, int>, std::deque<Send>> q;  // (from, to) FIFO, as RCCL matches
     std::vector<size_t> k(P, 0);
@@ -1204,6 +1280,47 @@ int sosx_loopback_allreduce(int alg, int P, int op, int datatype, void *const *s
     for (auto v : scr)
         if (v) (void)hipFree(v);
     return e == hipSuccess ? SOSX_OK : SOSX_ERR_HIP;
+}
+
+int sosx_loopback_allreduce(int alg, int P, int op, int datatype, void *const *srcs,
+                            void *const *dsts, size_t count, void *stream)
+{
+    if (P < 1 || P > SOSX_MAX_FOLD || !srcs || !dsts) return SOSX_ERR_ARG;
+    // broadcast, fcollect and alltoall move bytes: any sized type, no (op, type) rule;
+    // srcs[p] and dsts[p] span the plan's extents (sosx_plan_extents)
+    const bool moves = sosplan::is_bcast(alg) || sosplan::is_fcollect(alg) || sosplan::is_alltoall(alg);
+    int rc = moves ? (sos_dtype_info(datatype).size ? SOSX_OK : SOSX_ERR_DTYPE)
+                   : sos_check_op(op, datatype);
+    if (rc) return rc;
+    if (sosplan::is_bcast(alg) && ((alg - sosplan::PLAN_BCAST) >> 1) >= P) return SOSX_ERR_ARG;
+    const size_t ts = sos_dtype_info(datatype).size;
+    hipStream_t sm = (hipStream_t)stream;
+    const int a = sosplan::resolve_alg(alg, count * ts, 16384);
+    std::vector<Plan> plans(P);
+    std::vector<void *> scr(P, nullptr);
+    for (int p = 0; p < P; ++p) {
+        rc = sosplan::build(a, P, p, count, ts, (unsigned)((uintptr_t)srcs[p] & 15),
+                            (unsigned)((uintptr_t)dsts[p] & 15), &plans[p]);
+        if (rc) return rc;
+        if (plans[p].scratch_bytes && hipMalloc(&scr[p], plans[p].scratch_bytes) != hipSuccess)
+            return SOSX_ERR_HIP;
+    }
+    return run_loopback(plans, srcs, dsts, scr, op, datatype, sm);
+}
+
+int sosx_loopback_collect(int P, void *const *srcs, void *const *dsts, const size_t *lens, void *stream)
+{
+    if (P < 1 || P > sosplan::PLAN_MAX_PE || !srcs || !dsts || !lens) return SOSX_ERR_ARG;
+    uint64_t l64[sosplan::PLAN_MAX_PE];
+    for (int p = 0; p < P; ++p) l64[p] = lens[p];
+    std::vector<Plan> plans(P);
+    std::vector<void *> scr(P, nullptr);
+    for (int p = 0; p < P; ++p) {
+        const int rc = sosplan::build_collect(P, p, l64, &plans[p]);
+        if (rc) return rc;
+        if ((lens[p] && !srcs[p]) || (plans[p].dst_bytes && !dsts[p])) return SOSX_ERR_ARG;
+    }
+    return run_loopback(plans, srcs, dsts, scr, SOSX_OP_SUM, SOSX_DT_UCHAR, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -22,6 +22,10 @@ makes their min/max compare signed -- and writes:
                                   mem and active-set forms, generics and overloads
   sos_amd/csrc/collects_gen.cpp   their definitions (src/collectives_c.c4:536-707)
 
+  include/shmem_collectv.h        24 shmem_<T>_collect prototypes, shmem_collectmem, the
+                                  active-set shmem_collect32/64, generics and overloads
+  sos_amd/csrc/collectv_gen.cpp   their definitions (src/collectives_c.c4:432-503)
+
 Run: python sos_amd/csrc/gen_bindings.py  (build() runs it; output is committed).
 """
 import os
@@ -277,8 +281,8 @@ def source():
 # fcollect / alltoall / alltoalls over the RMA table (SHMEM_BIND_C_RMA of SHMEM_DEF_FCOLLECT,
 # SHMEM_DEF_ALLTOALL, SHMEM_DEF_ALLTOALLS: src/collectives_c.c4:536-558, :609-631, :687-707)
 COLLECTS = ("fcollect", "alltoall", "alltoalls")
-_STRIDES = {"fcollect": "", "alltoall": "", "alltoalls": "ptrdiff_t dst, ptrdiff_t sst, "}
-_STRIDE_ARGS = {"fcollect": "", "alltoall": "", "alltoalls": "dst, sst, "}
+_STRIDES = {"fcollect": "", "alltoall": "", "alltoalls": "ptrdiff_t dst, ptrdiff_t sst, ", "collect": ""}
+_STRIDE_ARGS = {"fcollect": "", "alltoall": "", "alltoalls": "dst, sst, ", "collect": ""}
 
 
 def collect_sig(prefix, st, ct, kind):
@@ -368,6 +372,93 @@ def collect_symbols():
     return [f"shmem_{st}_{kind}" for kind in COLLECTS for st, ct in RMA]
 
 
+# collect (variable lengths) over the RMA table: SHMEM_BIND_C_RMA of SHMEM_DEF_COLLECT, plus
+# shmem_collectmem and the deprecated shmem_collect32/64 (src/collectives_c.c4:432-503).
+# Files of their own, beside shmem_collects.h / collects_gen.cpp.
+def collectv_active_sig(prefix, bits):
+    return (f"void {prefix}shmem_collect{bits}(void *target, const void *source, size_t nlong, "
+            f"int PE_start, int logPE_stride, int PE_size, long *pSync)")
+
+
+def collectv_header():
+    out = ["/* shmem_collectv.h -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.",
+           " *",
+           " * SOS's collect (concatenation of per-PE contributions of different lengths): the",
+           " * 24 typed team forms shmem_<T>_collect (src/collectives_c.c4:463-485),",
+           " * shmem_collectmem, the deprecated active-set shmem_collect32/64, the C11 generic",
+           " * selector and the C++ overloads.  Included from shmem.h. */",
+           "#ifndef SHMEM_COLLECTV_H", "#define SHMEM_COLLECTV_H", "",
+           "#ifdef __cplusplus", 'extern "C" {', "#endif", ""]
+    for st, ct in RMA:
+        out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_sig('', st, ct, 'collect')};")
+    out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_mem_sig('', 'collect')};")
+    for bits in (32, 64):
+        out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collectv_active_sig('', bits)};")
+    out.append("")
+    out.append("/* profiling interface: pshmem_* are the implementations, shmem_* weak aliases */")
+    for st, ct in RMA:
+        out.append(f"{collect_sig('p', st, ct, 'collect')};")
+    out.append(f"{collect_mem_sig('p', 'collect')};")
+    for bits in (32, 64):
+        out.append(f"{collectv_active_sig('p', bits)};")
+    out += ["", "#ifdef __cplusplus", "}  /* extern \"C\" */", "#endif", ""]
+    out.append("#if defined(__cplusplus)")
+    for st, ct in GENERIC_RMA:
+        out.append(f"static inline int shmem_collect(shmem_team_t team, {ct} *dest, const {ct} *source, "
+                   f"size_t nelems) {{ return shmem_{st}_collect(team, dest, source, nelems); }}")
+    out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
+    out.append("#ifndef SHMEM_C11_TYPE_EVAL_PTR")
+    out.append("#define SHMEM_C11_TYPE_EVAL_PTR(arg) &*(arg)")
+    out.append("#define SHMEM_C11_ARG1(first, ...) SHMEM_C11_ARG1_HELPER(__VA_ARGS__, sentinel)")
+    out.append("#define SHMEM_C11_ARG1_HELPER(second, ...) second")
+    out.append("#endif")
+    out += c11_generic("shmem_collect", [f"        {ct}*: shmem_{st}_collect" for st, ct in GENERIC_RMA])
+    out.append("#endif")
+    out += ["", "#endif /* SHMEM_COLLECTV_H */", ""]
+    return "\n".join(out)
+
+
+def collectv_source():
+    out = ["// collectv_gen.cpp -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.",
+           "//",
+           "// The 24 typed collect entry points (SHMEM_DEF_COLLECT over SHMEM_BIND_C_RMA),",
+           "// shmem_collectmem and the active-set shmem_collect32/64",
+           "// (src/collectives_c.c4:432-503): strong pshmem_*, weak shmem_* aliases.",
+           '#include "shmem.h"', '#include "api_internal.h"', "",
+           'extern "C" {', ""]
+    for st, ct in RMA:
+        name = f"shmem_{st}_collect"
+        out.append(f"{collect_sig('p', st, ct, 'collect')}")
+        out.append("{")
+        out.append(f"    return sos_api_collect(team, dest, source, nelems, sizeof({ct}), \"{name}\");")
+        out.append("}")
+        out.append(f"{collect_sig('', st, ct, 'collect')} __attribute__((weak, alias(\"p{name}\")));")
+        out.append("")
+    out.append(f"{collect_mem_sig('p', 'collect')}")
+    out.append("{")
+    out.append('    return sos_api_collect(team, dest, source, nelems, 1, "shmem_collectmem");')
+    out.append("}")
+    out.append(f"{collect_mem_sig('', 'collect')} __attribute__((weak, alias(\"pshmem_collectmem\")));")
+    out.append("")
+    for bits in (32, 64):
+        name = f"shmem_collect{bits}"
+        out.append(f"{collectv_active_sig('p', bits)}")
+        out.append("{")
+        out.append(f"    sos_api_collect_active(target, source, nlong, {bits // 8}, PE_start, logPE_stride, "
+                   f"PE_size, pSync, \"{name}\");")
+        out.append("}")
+        out.append(f"{collectv_active_sig('', bits)} __attribute__((weak, alias(\"p{name}\")));")
+        out.append("")
+    out += ['}  // extern "C"', ""]
+    return "\n".join(out)
+
+
+def collectv_symbols():
+    """The generated collect names: typed, mem and active-set forms."""
+    return ([f"shmem_{st}_collect" for st, ct in RMA] + ["shmem_collectmem", "shmem_collect32",
+                                                         "shmem_collect64"])
+
+
 def symbols():
     """All generated public names (used by the ABI test)."""
     return ([f"shmem_{st}_{op}_to_all" for (st, ct, it), op in TO_ALL]
@@ -383,7 +474,9 @@ def main():
                os.path.join(ROOT, "include", "shmemx_scans.h"): scan_header(),
                os.path.join(ROOT, "sos_amd", "csrc", "reductions_gen.cpp"): source(),
                os.path.join(ROOT, "include", "shmem_collects.h"): collects_header(),
-               os.path.join(ROOT, "sos_amd", "csrc", "collects_gen.cpp"): collects_source()}
+               os.path.join(ROOT, "sos_amd", "csrc", "collects_gen.cpp"): collects_source(),
+               os.path.join(ROOT, "include", "shmem_collectv.h"): collectv_header(),
+               os.path.join(ROOT, "sos_amd", "csrc", "collectv_gen.cpp"): collectv_source()}
     check = "--check" in sys.argv
     stale = False
     for path, text in targets.items():

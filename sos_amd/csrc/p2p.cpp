@@ -564,7 +564,7 @@ struct HipBackend {
 }  // namespace
 
 int p2p_exec(const sosplan::Plan &plan, const Team &t, int alg, uint64_t count, uint64_t ts,
-             const P2PBufs &b, int op, int dt, hipStream_t stream)
+             const P2PBufs &b, int op, int dt, hipStream_t stream, const uint64_t *lens)
 {
     State &s = st();
     P2PShared *sh = shared();
@@ -576,7 +576,7 @@ int p2p_exec(const sosplan::Plan &plan, const Team &t, int alg, uint64_t count, 
     auto world_of = [&](int i) { return t.world_rank(i); };
     if (g_sig.on) {
         const int rc = sosp2p::exec_stream(plan, t.size, t.my_idx, world_of, alg, count, ts, pb, sh,
-                                           g_sig.sl, be);
+                                           g_sig.sl, be, lens);
         if (tr && ++g_trace.calls % g_trace.every == 0) {
             const double k = 1e6 / (double)g_trace.every;
             fprintf(stderr, "[%04d] p2p trace, stream mode (calls %ld-%ld, us/call): descriptors %.1f "
@@ -588,7 +588,7 @@ int p2p_exec(const sosplan::Plan &plan, const Team &t, int alg, uint64_t count, 
         }
         return rc;
     }
-    const int rc = sosp2p::exec_host(plan, t.size, t.my_idx, world_of, alg, count, ts, pb, sh, g_local, be);
+    const int rc = sosp2p::exec_host(plan, t.size, t.my_idx, world_of, alg, count, ts, pb, sh, g_local, be, lens);
     if (tr && ++g_trace.calls % g_trace.every == 0) {  // window averages, then reset
         const double k = 1e6 / (double)g_trace.every;
         fprintf(stderr, "[%04d] p2p trace (calls %ld-%ld, us/call): sync-send %.1f wait-post %.1f "

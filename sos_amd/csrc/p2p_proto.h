@@ -129,23 +129,32 @@ struct PeerSend {
 };
 
 // The sends peer q's plan makes to `me`, in order (deterministic: rebuild q's plan from
-// its published operand misalignment, which places its scratch slots).  Empty with
-// *ok = false when q's plan cannot be built.
+// its published operand misalignment, which places its scratch slots, and for a collect
+// from the call's P byte lengths `lens`, which every PE holds).  Empty with *ok = false
+// when q's plan cannot be built.
 inline const std::vector<PeerSend> &peer_sends(int alg, int P, int q, int me, uint64_t count,
-                                               uint64_t ts, uint64_t mis, bool *ok)
+                                               uint64_t ts, uint64_t mis, bool *ok,
+                                               const uint64_t *lens = nullptr)
 {
-    static thread_local std::map<std::tuple<int, int, int, int, uint64_t, uint64_t, uint64_t>,
+    static thread_local std::map<std::tuple<int, int, int, int, uint64_t, uint64_t, uint64_t,
+                                            std::vector<uint64_t>>,
                                  std::vector<PeerSend>> cache;
     *ok = true;
-    auto key = std::make_tuple(alg, P, q, me, count, ts, mis);
+    static thread_local std::vector<PeerSend> none;
+    if (sosplan::is_collect(alg) && (!lens || P < 1 || P > sosplan::PLAN_MAX_PE)) {
+        *ok = false;
+        return none;
+    }
+    auto key = std::make_tuple(alg, P, q, me, count, ts, mis,
+                               sosplan::is_collect(alg) ? std::vector<uint64_t>(lens, lens + P)
+                                                        : std::vector<uint64_t>());
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
     if (cache.size() > 512) cache.clear();
     sosplan::Plan p;
     std::vector<PeerSend> v;
-    if (sosplan::build(alg, P, q, count, ts, (unsigned)(mis & 15), (unsigned)(mis >> 4), &p) != SOSX_OK) {
+    if (sosplan::build(alg, P, q, count, ts, (unsigned)(mis & 15), (unsigned)(mis >> 4), &p, lens) != SOSX_OK) {
         *ok = false;
-        static thread_local std::vector<PeerSend> none;
         return none;
     }
     for (const auto &r : p.rounds)
@@ -195,7 +204,8 @@ inline bool round_fusable(const sosplan::Round &r, uint64_t ts, const LocalPtr &
 //   void phase(int)                                        tracing (may be a no-op)
 template <class B, class WorldOf>
 int exec_host(const sosplan::Plan &plan, int P, int me, const WorldOf &world_of, int alg,
-              uint64_t count, uint64_t ts, const Bufs &b, Shared *sh, Local &loc, B &be)
+              uint64_t count, uint64_t ts, const Bufs &b, Shared *sh, Local &loc, B &be,
+              const uint64_t *lens = nullptr)
 {
     enum { PH_SYNC_SEND, PH_WAIT_POST, PH_ENQUEUE, PH_SYNC_OPS, PH_WAIT_CONSUMED, PH_SYNC_END };
     const int my_world = world_of(me);
@@ -241,7 +251,8 @@ int exec_host(const sosplan::Plan &plan, int P, int me, const WorldOf &world_of,
             const uint64_t dst_off = sh->pub[pw].dst_off.load(std::memory_order_acquire);
             bool ok;
             const auto &sends = peer_sends(alg, P, x.peer, me, count, ts,
-                                           sh->pub[pw].mis.load(std::memory_order_relaxed), &ok);
+                                           sh->pub[pw].mis.load(std::memory_order_relaxed), &ok,
+                                           lens);
             const int k = recv_idx[(size_t)x.peer]++;
             if (!ok || k >= (int)sends.size() || sends[(size_t)k].bytes != x.bytes) be.plan_mismatch(pw);
             const PeerSend &ps = sends[(size_t)k];
@@ -331,7 +342,8 @@ int exec_host(const sosplan::Plan &plan, int P, int me, const WorldOf &world_of,
 //   bool device_wait_failed()         a queued wait timed out (after complete())
 template <class B, class WorldOf>
 int exec_stream(const sosplan::Plan &plan, int P, int me, const WorldOf &world_of, int alg,
-                uint64_t count, uint64_t ts, const Bufs &b, Shared *sh, StreamLocal &sl, B &be)
+                uint64_t count, uint64_t ts, const Bufs &b, Shared *sh, StreamLocal &sl, B &be,
+                const uint64_t *lens = nullptr)
 {
     enum { PH_WAIT_POST = 1, PH_ENQUEUE = 2, PH_SYNC_END = 5 };
     const int my_world = world_of(me);
@@ -462,7 +474,7 @@ int exec_stream(const sosplan::Plan &plan, int P, int me, const WorldOf &world_o
             const int pw = world_of(x.peer);
             const Desc &d = peer_desc[(size_t)x.peer];
             bool ok;
-            const auto &sends = peer_sends(alg, P, x.peer, me, count, ts, d.mis, &ok);
+            const auto &sends = peer_sends(alg, P, x.peer, me, count, ts, d.mis, &ok, lens);
             const int k = recv_idx[(size_t)x.peer]++;
             if (!ok || k >= (int)sends.size() || sends[(size_t)k].bytes != x.bytes) be.plan_mismatch(pw);
             const PeerSend &ps = sends[(size_t)k];

@@ -494,6 +494,37 @@ int build_alltoall(int P, int me, uint64_t B, Plan *plan)
 
 }  // namespace
 
+int build_collect(int P, int me, const uint64_t *len, Plan *plan)
+{
+    if (!plan || !len || P < 1 || P > PLAN_MAX_PE || me < 0 || me >= P) return SOSX_ERR_ARG;
+    uint64_t off[PLAN_MAX_PE], sum = 0;
+    for (int q = 0; q < P; ++q) {
+        off[q] = sum;
+        if (len[q] > UINT64_MAX - sum) return SOSX_ERR_ARG;
+        sum += len[q];
+    }
+    plan->alg = PLAN_COLLECT;
+    plan->rounds.clear();
+    plan->scratch_bytes = 0;
+    plan->reads_src = plan->writes_dst = true;
+    plan->scr_sent = false;
+    plan->src_bytes = len[me];
+    plan->dst_bytes = sum;
+    if (len[me]) {
+        Round c;
+        c.ops.push_back(copy_op(DST, off[me], SRC, 0, len[me]));
+        plan->rounds.push_back(c);
+    }
+    Round ag;
+    for (int k = 1; k < P; ++k) {
+        const int peer = (me + k) % P;
+        if (len[me]) ag.xfers.push_back(xf(1, peer, DST, off[me], len[me]));
+        if (len[peer]) ag.xfers.push_back(xf(0, peer, DST, off[peer], len[peer]));
+    }
+    if (!ag.xfers.empty()) plan->rounds.push_back(ag);
+    return SOSX_OK;
+}
+
 int extents(int alg, int P, uint64_t count, uint64_t ts, uint64_t *src_bytes, uint64_t *dst_bytes)
 {
     const bool known = (alg >= SOSX_ALG_AUTO && alg <= SOSX_ALG_RECDBL_GATHER) || is_scan(alg) ||
@@ -533,8 +564,9 @@ int resolve_alg(int alg, uint64_t bytes, uint64_t crossover)
 }
 
 int build(int alg, int P, int me, uint64_t count, uint64_t ts, unsigned src_mis,
-          unsigned dst_mis, Plan *out)
+          unsigned dst_mis, Plan *out, const uint64_t *lens)
 {
+    if (is_collect(alg)) return build_collect(P, me, lens, out);
     if (!out || P < 1 || me < 0 || me >= P || ts == 0) return SOSX_ERR_ARG;
     out->alg = alg;
     out->rounds.clear();
@@ -606,13 +638,8 @@ int build(int alg, int P, int me, uint64_t count, uint64_t ts, unsigned src_mis,
 //                      nout, nout * (buf, off))]
 // Returns the number of words (the buffer is filled only if cap >= that), or < 0.
 // --------------------------------------------------------------------------------
-extern "C" long long sosx_plan_encode(int alg, int P, int me, unsigned long long count,
-                                      unsigned long long ts, unsigned src_mis,
-                                      unsigned dst_mis, long long *out, unsigned long long cap)
+static long long encode_plan(const sosplan::Plan &p, long long *out, unsigned long long cap)
 {
-    sosplan::Plan p;
-    int rc = sosplan::build(alg, P, me, count, ts, src_mis, dst_mis, &p);
-    if (rc) return rc;
     std::vector<long long> w;
     w.push_back(p.alg);
     w.push_back((long long)p.rounds.size());
@@ -647,6 +674,34 @@ extern "C" long long sosx_plan_encode(int alg, int P, int me, unsigned long long
     }
     if (out && cap >= w.size()) memcpy(out, w.data(), w.size() * sizeof(long long));
     return (long long)w.size();
+}
+
+extern "C" long long sosx_plan_encode(int alg, int P, int me, unsigned long long count,
+                                      unsigned long long ts, unsigned src_mis,
+                                      unsigned dst_mis, long long *out, unsigned long long cap)
+{
+    sosplan::Plan p;
+    // a collect plan needs the lengths: sosx_plan_encode_collect
+    int rc = sosplan::is_collect(alg) ? SOSX_ERR_ARG
+                                      : sosplan::build(alg, P, me, count, ts, src_mis, dst_mis, &p);
+    if (rc) return rc;
+    return encode_plan(p, out, cap);
+}
+
+// The collect plan of PE `me` for the P byte lengths `lens`, in sosx_plan_encode's words,
+// with the plan's extents (src_bytes = lens[me], dst_bytes = the sum) when asked for.
+extern "C" long long sosx_plan_encode_collect(int P, int me, const unsigned long long *lens,
+                                              unsigned long long *src_bytes,
+                                              unsigned long long *dst_bytes, long long *out,
+                                              unsigned long long cap)
+{
+    sosplan::Plan p;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "length words");
+    int rc = sosplan::build_collect(P, me, (const uint64_t *)lens, &p);
+    if (rc) return rc;
+    if (src_bytes) *src_bytes = p.src_bytes;
+    if (dst_bytes) *dst_bytes = p.dst_bytes;
+    return encode_plan(p, out, cap);
 }
 
 extern "C" int sosx_plan_extents(int alg, int P, unsigned long long count, unsigned long long ts,

@@ -36,6 +36,11 @@
 //   ALLTOALL      block q of the source to PE q (src/collectives.c:1449-1480): one direct
 //                 exchange round, then the self block.  alltoalls runs this plan over
 //                 packed operands (collectives.cpp).
+//   COLLECT       every PE's contribution of its OWN length in PE order
+//                 (src/collectives.c:1215-1276): the own copy to the exclusive prefix of
+//                 the lengths, then one direct uneven allgather inside DST.  The only plan
+//                 that depends on more than (alg, P, me, count, ts, mis): the P byte
+//                 lengths, which every PE must hold before it builds (build_collect).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -61,12 +66,15 @@ constexpr int PLAN_EXSCAN = 17;
 // plans whose SRC and DST extents differ from count * ts (Plan::src_bytes / dst_bytes).
 constexpr int PLAN_FCOLLECT = 18;
 constexpr int PLAN_ALLTOALL = 19;
+// collect: per-PE byte lengths instead of count * ts (build_collect / build's `lens`)
+constexpr int PLAN_COLLECT = 20;
 constexpr int PLAN_BCAST = 32;
 constexpr int PLAN_MAX_PE = 64;   // inputs of one local op: SOSX_MAX_FOLD folds, scan prefixes
 inline bool is_scan(int alg) { return alg == PLAN_INSCAN || alg == PLAN_EXSCAN; }
 inline bool is_bcast(int alg) { return alg >= PLAN_BCAST; }
 inline bool is_fcollect(int alg) { return alg == PLAN_FCOLLECT; }
 inline bool is_alltoall(int alg) { return alg == PLAN_ALLTOALL; }
+inline bool is_collect(int alg) { return alg == PLAN_COLLECT; }
 inline int bcast_alg(int root, bool copy_root) { return PLAN_BCAST + 2 * root + (copy_root ? 1 : 0); }
 
 struct Xfer {
@@ -101,8 +109,9 @@ struct Plan {
     int alg = 0;
     std::vector<Round> rounds;
     uint64_t scratch_bytes = 0;
-    uint64_t src_bytes = 0;    // extent of SRC (count * ts; alltoall: P * count * ts)
-    uint64_t dst_bytes = 0;    // extent of DST (count * ts; fcollect, alltoall: P * count * ts)
+    uint64_t src_bytes = 0;    // extent of SRC (count * ts; alltoall: P * count * ts; collect: len[me])
+    uint64_t dst_bytes = 0;    // extent of DST (count * ts; fcollect, alltoall: P * count * ts;
+                               // collect: the sum of the lengths)
     bool reads_src = true;     // false: a broadcast non-root never reads its source
     bool writes_dst = true;    // false: a broadcast root without copy leaves its target
     bool scr_sent = false;     // true: some transfer sends out of SCR (scans)
@@ -120,9 +129,19 @@ void ring_chunk(uint64_t count, int P, int c, uint64_t *n, uint64_t *first);
 // PLAN_FCOLLECT / PLAN_ALLTOALL (P <= PLAN_MAX_PE)
 // or bcast_alg(root, copy_root) (src/collectives.c:429-551 bcast_linear/tree).  src_mis/dst_mis = caller pointer addresses mod 16, so scratch
 // slots can be placed 16-B congruent with the caller's chunks (vector path).
+// PLAN_COLLECT takes the P per-PE byte lengths in `lens` (count, ts and the misalignments
+// are not used); every other plan ignores `lens`.
 // Returns SOSX_OK or SOSX_ERR_ARG.
 int build(int alg, int P, int me, uint64_t count, uint64_t ts, unsigned src_mis,
-          unsigned dst_mis, Plan *out);
+          unsigned dst_mis, Plan *out, const uint64_t *lens = nullptr);
+
+// The collect plan of team index `me` for per-PE byte lengths len_bytes[0..P), P <=
+// PLAN_MAX_PE.  With off[q] the exclusive prefix of the lengths: round 0 copies SRC to
+// DST + off[me]; round 1, for each peer in fcollect's order (me + k) % P, sends
+// DST + off[me] and receives DST + off[peer].  A zero length sends, receives and copies
+// nothing, and a round left empty is not emitted.  src_bytes = len[me], dst_bytes = the
+// sum; no scratch.  SOSX_ERR_ARG also when the sum does not fit 64 bits.
+int build_collect(int P, int me, const uint64_t *len_bytes, Plan *out);
 
 // Extents in bytes of SRC and DST for plan `alg` (what build() records in the plan).
 // SOSX_ERR_ARG: no such plan id, P < 1, ts == 0, or a product that does not fit 64 bits.

@@ -92,6 +92,7 @@ struct State {
     long acquire_kernels = 0;         // of sys_acquires: stream-wide acquire kernels
     bool acq_pending = false;         // a peer wait since the last acquire (stream order)
     unsigned *acq_mask = nullptr;     // device word: XCD ids the acquire kernels ran on
+    uint64_t *collect_lens = nullptr; // pinned: collect's internal lengths fcollect (collectives.cpp)
     void *stripes = nullptr;
     size_t stripes_bytes = 0;
     size_t host_stripe_bytes = 256u << 10; // SHMEMX_HOST_STRIPE_BYTES: min slice (0 = off)
@@ -230,6 +231,12 @@ bool small_path_route(int alg, const void *target, const void *source, size_t by
                       bool allowed, const char *fn);
 void small_path_reduce(int alg, void *target, const void *source, size_t count, size_t ts,
                        const Team &t, int op, int dt, const char *fn);
+// collect through the shared segment (smallpath.cpp): headers carry the lengths, and the
+// payloads when every PE's fits; exchange, the caller's extent checks, then finish
+bool small_collect_exchange(const Team &t, const void *source, size_t bytes, uint64_t *lens,
+                            bool *all_payload, const char *fn);
+void small_collect_finish(const Team &t, void *target, const uint64_t *lens, bool take, const char *fn);
+long small_collect_calls();
 long small_path_calls();
 long small_path_device_calls();
 size_t small_path_set_device_bytes(size_t team_bytes);
@@ -261,6 +268,7 @@ struct P2PBufs {
     size_t scr_off;           // heap offset of scr when the plan sends out of it
     unsigned smis, dmis;      // src/dst address mod 16 the plan was built with
 };
+// `lens`: the P per-PE byte lengths of a collect plan (the peers' plans are rebuilt from them)
 int p2p_exec(const sosplan::Plan &plan, const Team &t, int alg, uint64_t count, uint64_t ts,
-             const P2PBufs &b, int op, int dt, hipStream_t stream);
+             const P2PBufs &b, int op, int dt, hipStream_t stream, const uint64_t *lens = nullptr);
 }  // namespace sosrt

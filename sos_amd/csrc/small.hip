@@ -270,6 +270,101 @@ __global__ __launch_bounds__(kStageThreads) void k_small_stage(A a)
         __hip_atomic_store(a.word[threadIdx.x], a.val[threadIdx.x], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// Concatenation of np <= 64 segments of arbitrary byte lengths into `out` (collect's small
+// path, smallpath.cpp): segment q lands at out + off[q], off the exclusive prefix of the
+// lengths, so source and destination are in general incongruent mod 16.  Workgroups are
+// dealt per segment in proportion to its bytes -- segment q owns workgroups
+// [tstart[q], tstart[q + 1]), none when it is empty -- and a tile (kThreads * kCollectU
+// 16-B vectors, 16 KiB) never straddles a segment.  The destination is written on ITS
+// 16-B grid: up to 15 head bytes to the first boundary and up to 15 tail bytes go one
+// per lane in the segment's first workgroup, the vectors between them as 16-B stores.
+// The source of a vector sits at misalignment d: d = 0 loads it aligned, d on the 4-B
+// grid loads it unaligned (one global_load_dwordx4), any other d loads the two aligned
+// vectors around it and realigns (realign16); the second of those is the aligned vector
+// that holds the wanted vector's last byte, so no load leaves the 16-B granules the
+// segment occupies.  Every load of a tile, head and tail bytes included, is issued
+// before its first store.  Plain loads and stores, as the other small-path kernels: the
+// slots are host memory read once behind the acquire, and the result is read next by the
+// host or a DMA copy, which the completion fence serves.  Indices are 64-bit.
+constexpr int kCollectU = 4;
+struct SmallCollectArgs {
+    const void *src[SOSX_MAX_FOLD];
+    uint64_t off[SOSX_MAX_FOLD + 1];
+    uint32_t tstart[SOSX_MAX_FOLD + 1];
+    uint32_t *flags;
+    uint32_t seq;
+    int np;
+};
+
+__global__ __launch_bounds__(kThreads) void k_small_collect(uint8_t *out, SmallCollectArgs a)
+{
+    slot_acquire();
+    const uint32_t b = blockIdx.x;
+    int q = 0;
+    while (q + 1 < a.np && b >= a.tstart[q + 1]) ++q;
+    const uint64_t local = b - a.tstart[q];
+    const uint64_t len = a.off[q + 1] - a.off[q];
+    uint8_t *d0 = out + a.off[q];
+    const uint8_t *s = (const uint8_t *)a.src[q];
+    uint64_t head = (16 - ((uintptr_t)d0 & 15)) & 15;
+    if (head > len) head = len;
+    const uint64_t nvec = (len - head) / 16;
+    const uint64_t tail0 = head + nvec * 16;  // first byte after the vectors
+    const uint8_t *sb = s + head;
+    const unsigned d = (unsigned)((uintptr_t)sb & 15);
+    u32x4 *O = reinterpret_cast<u32x4 *>(d0 + head);
+    const uint64_t base = local * (uint64_t)(kThreads * kCollectU) + threadIdx.x;
+    // loads: the segment's ragged bytes (its first workgroup), then this tile's vectors
+    bool edge = false;
+    uint64_t ei = 0;
+    uint8_t eb = 0;
+    if (local == 0) {
+        if (threadIdx.x < head) {
+            edge = true;
+            ei = threadIdx.x;
+        } else if (threadIdx.x >= 16 && tail0 + (threadIdx.x - 16) < len) {
+            edge = true;
+            ei = tail0 + (threadIdx.x - 16);
+        }
+        if (edge) eb = s[ei];
+    }
+    u32x4 x[kCollectU];
+    if (d == 0) {
+#pragma unroll
+        for (int u = 0; u < kCollectU; ++u) {
+            const uint64_t v = base + (uint64_t)u * kThreads;
+            if (v < nvec) x[u] = reinterpret_cast<const u32x4 *>(sb)[v];
+        }
+    } else if ((d & 3) == 0) {
+#pragma unroll
+        for (int u = 0; u < kCollectU; ++u) {
+            const uint64_t v = base + (uint64_t)u * kThreads;
+            if (v < nvec) x[u] = *reinterpret_cast<const u32x4u *>(sb + 16 * v);
+        }
+    } else {
+        const u32x4 *I = reinterpret_cast<const u32x4 *>(sb - d);
+        u32x4 lo[kCollectU], hi[kCollectU];
+#pragma unroll
+        for (int u = 0; u < kCollectU; ++u) {
+            const uint64_t v = base + (uint64_t)u * kThreads;
+            if (v < nvec) {
+                lo[u] = I[v];
+                hi[u] = I[v + 1];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kCollectU; ++u) x[u] = realign16(lo[u], hi[u], d);
+    }
+    // stores
+#pragma unroll
+    for (int u = 0; u < kCollectU; ++u) {
+        const uint64_t v = base + (uint64_t)u * kThreads;
+        if (v < nvec) O[v] = x[u];
+    }
+    if (edge) d0[ei] = eb;
+    signal_done(a.flags, a.seq);
+}
+
 }  // namespace sos
 
 using namespace sos;
@@ -521,6 +616,47 @@ int sosx_small_stage(void *dst, const void *src, size_t bytes, uint64_t *const *
         hipLaunchKernelGGL((k_small_stage<SmallStageArgsT<SOSX_MAX_FOLD>>), dim3(1), dim3(kStageThreads), 0,
                            st, a);
     }
+    return hip_ok(hipGetLastError());
+}
+
+// out[off[q], off[q] + lens[q]) = segs[q][0, lens[q]) for q < np, off the exclusive prefix
+// of lens: one launch (k_small_collect); workgroup b then stores `seq` into flags[b],
+// b < *nblocks.  1 <= np <= SOSX_MAX_FOLD; a zero length needs no pointer; nothing outside
+// [out, out + sum) is written, and with every length zero nothing is launched
+// (*nblocks = 0).  flags must hold np + sum / 16 KiB words.
+int sosx_small_collect(void *out, const void *const *segs, const size_t *lens, int np,
+                       uint32_t *flags, uint32_t seq, int *nblocks, void *stream)
+{
+    if (np < 1 || np > SOSX_MAX_FOLD || !segs || !lens || !flags || !nblocks) return SOSX_ERR_ARG;
+    SmallCollectArgs a;
+    memset(&a, 0, sizeof(a));
+    uint64_t sum = 0, tiles = 0;
+    for (int q = 0; q < np; ++q) {
+        if (lens[q] && !segs[q]) return SOSX_ERR_ARG;
+        if (lens[q] > UINT64_MAX - sum) return SOSX_ERR_ARG;
+        a.src[q] = segs[q];
+        a.off[q] = sum;
+        a.tstart[q] = (uint32_t)tiles;
+        if (lens[q]) {
+            uint64_t head = (16 - (((uintptr_t)out + sum) & 15)) & 15;
+            if (head > lens[q]) head = lens[q];
+            const uint64_t nvec = (lens[q] - head) / 16, per = (uint64_t)kThreads * kCollectU;
+            tiles += nvec ? (nvec + per - 1) / per : 1;
+        }
+        sum += lens[q];
+        if (tiles >= kNoCap) return SOSX_ERR_ARG;
+    }
+    a.off[np] = sum;
+    a.tstart[np] = (uint32_t)tiles;
+    if (sum && !out) return SOSX_ERR_ARG;
+    *nblocks = 0;
+    if (tiles == 0) return SOSX_OK;
+    a.flags = flags;
+    a.seq = seq;
+    a.np = np;
+    hipLaunchKernelGGL(k_small_collect, dim3((unsigned)tiles), dim3(kThreads), 0, as_stream(stream),
+                       (uint8_t *)out, a);
+    *nblocks = (int)tiles;
     return hip_ok(hipGetLastError());
 }
 

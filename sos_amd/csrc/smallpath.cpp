@@ -56,6 +56,7 @@
 #include <string.h>
 #include <time.h>
 
+#include <algorithm>
 #include <atomic>
 #include <functional>
 #include <map>
@@ -133,6 +134,13 @@ struct Small {
     size_t dev_team_bytes = 0;   // device operands: P * bytes limit (0: host operands only)
     long calls = 0;
     long dev_calls = 0;          // of which with a device operand
+    // collect (small_collect_exchange / small_collect_finish)
+    bool collect_on = true;      // SHMEMX_SMALL_COLLECT != 0
+    size_t flag_words = 0;       // capacity of `flags`
+    long collect_calls = 0;      // collect calls that took the small path
+    int cx_from[kMaxPE];         // the exchange in flight: world PE of each member (-1: me)
+    const void *cx_seg[kMaxPE];  // its payloads, device view
+    bool cx_staged = false;      // my payload travels by the copy kernel
 };
 Small g;
 
@@ -270,6 +278,9 @@ void small_path_setup(void *region, size_t bytes)
     g.slot = slot;
     g.npes = s.n_pes;
     g.dev_team_bytes = env_size("SHMEMX_SMALL_DEVICE", kDeviceTeamBytes);
+    g.flag_words = flag_words;
+    const char *ec = getenv("SHMEMX_SMALL_COLLECT");
+    g.collect_on = !(ec && !strcmp(ec, "0"));
     g.ready = ok != 0;
     if (!g.ready) small_path_teardown();
     debug_msg("small shared-memory path: %s", g.ready ? "on" : "off");
@@ -590,6 +601,144 @@ void small_path_reduce(int alg, void *target, const void *source, size_t count, 
 }
 
 // ---------------------------------------------------------------------------------
+// collect (shmem_collect: per-PE lengths).  Every PE of the call posts a slot
+//   [header: len, has_payload (two uint64_t)][payload]
+// to the team through the slot, post and ack machinery above, with the same per-pair
+// counters, so the counts stay in step with the other small-path calls.  A PE attaches its
+// payload when len is at most a cap that depends only on the team size and the residency
+// of ITS source (collect_cap).  After a PE has seen all P headers -- read by the host
+// straight from shared memory, no GPU work -- it holds every length, and the call takes
+// the small path iff EVERY header carries a payload: all PEs read the same headers, so the
+// choice is uniform by construction and needs no route words.  Then one launch per PE
+// (sosx_small_collect) concatenates the P payloads into the target.  Otherwise the slots
+// are acknowledged and the caller runs PLAN_COLLECT with the lengths it now holds.
+// Two steps, because the caller checks the target's true extent between them.
+// ---------------------------------------------------------------------------------
+namespace {
+constexpr size_t kCollectHeader = 16;
+
+// Largest payload a PE attaches: the slot and kTeamBytes / P for host sources,
+// SHMEMX_SMALL_DEVICE / P for device sources, and in both cases no more than the largest
+// per-PE length at which the path was measured to beat both the executor route and an
+// fcollect of the same bytes by more than the spread (profiles/small_collect.json, P = 2
+// and 4 on one GPU): 64 KiB from host memory (the largest size
+// measured), 16 KiB from device memory (at 64 KiB and P = 2 it only ties fcollect).  The
+// sum must fit the pinned result slot and the launch's workgroups the completion words.
+constexpr size_t kCollectHostCap = 64 * 1024, kCollectDeviceCap = 16 * 1024;
+size_t collect_cap(int P, bool dev_src)
+{
+    if (g.slot <= kCollectHeader || (size_t)P + g.slot / 16384 + 1 > g.flag_words) return 0;
+    size_t cap = std::min(g.slot - kCollectHeader, std::min(kTeamBytes, g.slot) / (size_t)P);
+    cap = std::min(cap, kCollectHostCap);
+    if (dev_src) cap = std::min(cap, std::min(g.dev_team_bytes / (size_t)P, kCollectDeviceCap));
+    return cap;
+}
+}  // namespace
+
+long small_collect_calls() { return g.collect_calls; }
+
+// Step 1: post my header (and payload), take every peer's; lens[i] = member i's bytes.
+// false: no shared segment (or SHMEMX_SMALL_COLLECT=0), nothing done.  *all_payload: every
+// member attached its payload.
+bool small_collect_exchange(const Team &t, const void *source, size_t bytes, uint64_t *lens,
+                            bool *all_payload, const char *fn)
+{
+    if (!g.ready || !g.collect_on || t.size < 2 || t.size > kMaxPE || t.my_idx < 0) return false;
+    State &s = st();
+    const int P = t.size, me = t.my_idx, mw = s.my_pe;
+    const int sl = (int)(g.seq++ % 2);
+    for (const auto &u : g.slot_users[sl]) wait_ge(ctl(u.first)->consumed[mw].v, u.second, "a peer to read a slot");
+    g.slot_users[sl].clear();
+    const bool dev_src = bytes && is_device_ptr(source);
+    const bool has = bytes <= collect_cap(P, dev_src) && (!dev_src || is_local_device_ptr(source));
+    const bool staged = has && dev_src;
+    char *slot = g.host + slot_off(mw, sl);
+    const uint64_t hdr[2] = {bytes, has ? 1u : 0u};
+    memcpy(slot, hdr, sizeof(hdr));
+    if (has && bytes && !staged) memcpy(slot + kCollectHeader, source, bytes);
+    std::atomic_thread_fence(std::memory_order_release);
+    SmallCtl *mine = ctl(mw);
+    uint64_t *words[kMaxPE];
+    uint64_t vals[kMaxPE];
+    int nw = 0;
+    for (int i = 0; i < P; ++i) {
+        if (i == me) continue;
+        const int r = t.world_rank(i);
+        const uint64_t k = ++g.posted_to[r];
+        mine->ring[r][k % 2] = (uint32_t)sl;
+        if (staged) {
+            words[nw] = (uint64_t *)(g.dev + ((char *)&mine->posted[r].v - g.host));
+            vals[nw++] = k;
+        } else {
+            mine->posted[r].v.store(k, std::memory_order_release);
+        }
+        g.slot_users[sl].push_back({r, k});
+    }
+    if (staged) {
+        std::atomic_thread_fence(std::memory_order_seq_cst);  // header and slot ids before the launch
+        const int rc = sosx_small_stage(g.dev + slot_off(mw, sl) + kCollectHeader, source, bytes, words,
+                                        vals, nw, s.stream);
+        if (rc) raise_error("%s: small-path copy of a device operand failed (status %d)", fn, rc);
+    }
+    g.cx_staged = staged;
+    bool all = has;
+    for (int i = 0; i < P; ++i) {
+        g.cx_from[i] = -1;
+        if (i == me) {
+            lens[i] = bytes;
+            g.cx_seg[i] = g.dev + slot_off(mw, sl) + kCollectHeader;
+            continue;
+        }
+        const int q = t.world_rank(i);
+        const uint64_t k = ++g.seen_from[q];
+        wait_ge(ctl(q)->posted[mw].v, k, "a peer's collect header");
+        const int qs = (int)ctl(q)->ring[mw][k % 2];
+        uint64_t h[2];
+        memcpy(h, g.host + slot_off(q, qs), sizeof(h));
+        lens[i] = h[0];
+        all = all && h[1] != 0;
+        g.cx_seg[i] = g.dev + slot_off(q, qs) + kCollectHeader;
+        g.cx_from[i] = q;
+    }
+    *all_payload = all;
+    return true;
+}
+
+// Step 2 (after every small_collect_exchange that returned true): with `take`, the one
+// launch that writes target[0, sum); always the acknowledgement of the peers' slots.
+void small_collect_finish(const Team &t, void *target, const uint64_t *lens, bool take, const char *fn)
+{
+    State &s = st();
+    const int P = t.size;
+    SmallCtl *mine = ctl(s.my_pe);
+    if (take) {
+        size_t n[kMaxPE], sum = 0;
+        for (int i = 0; i < P; ++i) sum += n[i] = (size_t)lens[i];
+        const bool dev_dst = sum && is_device_ptr(target);
+        const bool direct = dev_dst ? is_local_device_ptr(target) : s.host_heap.contains(target, sum);
+        void *out = direct ? target : g.out;
+        if (++g.fseq == 0) g.fseq = 1;
+        int nblocks = 0;
+        const int rc = sosx_small_collect(out, g.cx_seg, n, P, g.flags, g.fseq, &nblocks, s.stream);
+        if (rc) raise_error("%s: small-path collect failed (status %d)", fn, rc);
+        if (nblocks > 0) note_peer_read(true);  // each workgroup behind its own acquire
+        wait_flags(g.flags, nblocks, g.fseq, fn);
+        if (!direct && sum) {
+            if (dev_dst) {
+                hip_check(hipMemcpyAsync(target, g.out, sum, hipMemcpyHostToDevice, s.stream), fn);
+                hip_check(sync_system(s.stream), fn);
+            } else {
+                memcpy(target, g.out, sum);
+            }
+        }
+        g.collect_calls++;
+    }
+    for (int i = 0; i < P; ++i)
+        if (g.cx_from[i] >= 0)
+            mine->consumed[g.cx_from[i]].v.store(g.seen_from[g.cx_from[i]], std::memory_order_release);
+}
+
+// ---------------------------------------------------------------------------------
 // Small local combines (shmemx_reduce_local, shmem_internal_reduce_local's slot in this
 // build): one launch of the LINEAR two-operand fold, out = inout OP in, with completion
 // words instead of a stream synchronisation.  Host operands in the host symmetric heap
@@ -653,6 +802,7 @@ void small_local_release()
 
 }  // namespace sosrt
 
+extern "C" long sosx_small_collect_calls(void) { return sosrt::small_collect_calls(); }
 extern "C" long sosx_small_path_calls(void) { return sosrt::small_path_calls(); }
 extern "C" long sosx_small_path_device_calls(void) { return sosrt::small_path_device_calls(); }
 extern "C" size_t sosx_set_small_device_bytes(size_t team_bytes)

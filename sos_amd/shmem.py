@@ -49,6 +49,11 @@ _RUNTIME = {
     "sosx_plan_encode": (_c.c_longlong, [_c.c_int, _c.c_int, _c.c_int, _c.c_ulonglong,
                                          _c.c_ulonglong, _c.c_uint, _c.c_uint,
                                          _c.POINTER(_c.c_longlong), _c.c_ulonglong]),
+    "sosx_plan_encode_collect": (_c.c_longlong, [_c.c_int, _c.c_int, _c.POINTER(_c.c_ulonglong),
+                                                 _c.POINTER(_c.c_ulonglong), _c.POINTER(_c.c_ulonglong),
+                                                 _c.POINTER(_c.c_longlong), _c.c_ulonglong]),
+    "sosx_loopback_collect": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
+                                         _c.POINTER(_c.c_size_t), _c.c_void_p]),
     "sosx_resolve_alg": (_c.c_int, [_c.c_int, _c.c_ulonglong, _c.c_ulonglong]),
     "shmem_broadcastmem": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int]),
     "shmem_broadcast32": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
@@ -59,6 +64,11 @@ _RUNTIME = {
     "shmem_alltoallmem": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t]),
     "shmem_alltoallsmem": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_ssize_t,
                                       _c.c_ssize_t, _c.c_size_t]),
+    "shmem_collectmem": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t]),
+    "shmem_collect32": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
+                               _c.c_void_p]),
+    "shmem_collect64": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
+                               _c.c_void_p]),
     "shmem_fcollect32": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
                                 _c.c_void_p]),
     "shmem_fcollect64": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
@@ -79,7 +89,7 @@ _RUNTIME = {
 _REDUCE_RE = re.compile(r"^shmem_(\w+?)_(and|or|xor|min|max|sum|prod)_(reduce|to_all)$")
 _SCAN_RE = re.compile(r"^shmemx_(\w+?)_sum_(inscan|exscan)$")
 _BCAST_RE = re.compile(r"^shmem_(\w+?)_broadcast$")
-_COLLECT_RE = re.compile(r"^shmem_(\w+?)_(fcollect|alltoalls|alltoall)$")
+_COLLECT_RE = re.compile(r"^shmem_(\w+?)_(fcollect|alltoalls|alltoall|collect)$")
 _declared = False
 
 
@@ -133,7 +143,7 @@ def __getattr__(name):
         return fn
     m = _COLLECT_RE.match(name)
     if m and name not in _RUNTIME:
-        # shmem_<T>_fcollect / _alltoall (team, dest, source, nelems) and
+        # shmem_<T>_fcollect / _alltoall / _collect (team, dest, source, nelems) and
         # shmem_<T>_alltoalls (team, dest, source, dst, sst, nelems)
         fn = getattr(L, name)
         fn.restype = ctypes.c_int
@@ -174,7 +184,35 @@ def plan(alg, P, me, count, ts, src_mis=0, dst_mis=0):
         raise _lib.SosError(int(n), "sosx_plan_encode")
     buf = (ctypes.c_longlong * n)()
     L.sosx_plan_encode(a, P, me, count, ts, src_mis, dst_mis, buf, n)
-    w = list(buf)
+    return _decode_plan(list(buf))
+
+
+def plan_collect(P, me, lens):
+    """The collect plan of PE `me` for the per-PE byte lengths `lens`
+    (sosx_plan_encode_collect), with its "src_bytes" and "dst_bytes"."""
+    L = lib()
+    arr = (ctypes.c_ulonglong * max(len(lens), 1))(*lens)
+    sb, db = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+    n = L.sosx_plan_encode_collect(P, me, arr, ctypes.byref(sb), ctypes.byref(db), None, 0)
+    if n < 0:
+        raise _lib.SosError(int(n), "sosx_plan_encode_collect")
+    buf = (ctypes.c_longlong * n)()
+    L.sosx_plan_encode_collect(P, me, arr, None, None, buf, n)
+    out = _decode_plan(list(buf))
+    out.update(src_bytes=sb.value, dst_bytes=db.value)
+    return out
+
+
+def loopback_collect(srcs, dsts, lens, stream=None):
+    """All P collect plans on one GPU (sosx_loopback_collect); lens in bytes."""
+    P = len(lens)
+    s = (ctypes.c_void_p * P)(*srcs)
+    d = (ctypes.c_void_p * P)(*dsts)
+    n = (ctypes.c_size_t * P)(*lens)
+    return _lib.check(lib().sosx_loopback_collect(P, s, d, n, stream), "sosx_loopback_collect")
+
+
+def _decode_plan(w):
     pos = 3
     rounds = []
     for _ in range(w[1]):
