@@ -123,19 +123,11 @@ struct OpXor {
 // long double: the chosen operand's 10 value bytes, the left operand's padding.
 struct OpMax {
     template <class T> __device__ __forceinline__ static T f(T a, T b) { return a > b ? a : b; }
-    __device__ __forceinline__ static ld80 f(ld80 a, ld80 b)
-    {
-        const ld80 &c = x87::gt(a, b) ? a : b;
-        return x87::make(a, x87::se(c), c.m);
-    }
+    __device__ __forceinline__ static ld80 f(ld80 a, ld80 b) { return x87::max(a, b); }
 };
 struct OpMin {
     template <class T> __device__ __forceinline__ static T f(T a, T b) { return a < b ? a : b; }
-    __device__ __forceinline__ static ld80 f(ld80 a, ld80 b)
-    {
-        const ld80 &c = x87::gt(b, a) ? a : b;  // (a) < (b) ? (a) : (b)
-        return x87::make(a, x87::se(c), c.m);
-    }
+    __device__ __forceinline__ static ld80 f(ld80 a, ld80 b) { return x87::min(a, b); }
 };
 struct OpSum {
     template <class T> __device__ __forceinline__ static T f(T a, T b)

@@ -9,8 +9,11 @@
 //            underflow (denormals rounded at their own position), overflow to inf;
 //   min/max  the ternary compare (`a > b ? a : b`): unordered -> the right operand;
 //   specials inf - inf, 0 * inf and unsupported encodings (unnormals, pseudo-NaN/inf)
-//            give the x87 default NaN (0xFFFF:C000000000000000); a NaN operand is
-//            returned quieted.
+//            give the x87 default NaN (0xFFFF:C000000000000000); a NaN operand of
+//            add/mul is returned quieted, of two NaN operands the one whose stored
+//            significand is larger (a quiet NaN before a signalling one), on equal
+//            significands the positive one; min/max return the chosen operand as stored.
+// tests/ldbl_x87_harness.cpp runs these functions on the host against the CPU's own FPU.
 // The 6 padding bytes of a 16-byte long double are not written by the x87 store
 // (fstpt writes 10 bytes), so results keep the left operand's padding bytes.
 #pragma once
@@ -51,11 +54,14 @@ __device__ __forceinline__ bool is_zero(const ld80 &a) { return (se(a) & 0x7FFF)
 
 __device__ __forceinline__ ld80 default_nan(const ld80 &pad) { return make(pad, 0xFFFF, 0xC000000000000000ull); }
 
-// NaN operand(s): the NaN (larger significand of two) comes back quieted.
+// NaN operand(s): the NaN comes back quieted.  Of two NaNs the FPU returns the one with
+// the larger significand as stored (before quieting, so a quiet NaN beats a signalling
+// one whatever their payloads); on equal significands the positive one.
 __device__ __forceinline__ ld80 nan_result(const ld80 &a, const ld80 &b)
 {
     const bool na = is_nan(a), nb = is_nan(b);
-    const ld80 &w = (na && nb) ? ((b.m | (1ull << 62)) > (a.m | (1ull << 62)) ? b : a) : (na ? a : b);
+    const bool take_b = (na && nb) ? (b.m > a.m || (b.m == a.m && (se(a) >> 15))) : nb;
+    const ld80 &w = take_b ? b : a;
     return make(a, se(w), w.m | (1ull << 62));
 }
 
@@ -179,6 +185,21 @@ __device__ __forceinline__ bool gt(const ld80 &a, const ld80 &b)
     const bool mag_gt = ea != eb ? ea > eb : a.m > b.m;
     const bool mag_eq = ea == eb && a.m == b.m;
     return sa ? (!mag_gt && !mag_eq) : mag_gt;
+}
+
+// (a) > (b) ? (a) : (b) and (a) < (b) ? (a) : (b): `b` on ties and whenever the compare
+// is unordered; the chosen operand's 10 value bytes as they are (a NaN is not quieted,
+// an unsupported encoding stays: fld/fstp of an 80-bit value converts nothing), the
+// left operand's padding.
+__device__ __forceinline__ ld80 max(const ld80 &a, const ld80 &b)
+{
+    const ld80 &c = gt(a, b) ? a : b;
+    return make(a, se(c), c.m);
+}
+__device__ __forceinline__ ld80 min(const ld80 &a, const ld80 &b)
+{
+    const ld80 &c = gt(b, a) ? a : b;
+    return make(a, se(c), c.m);
 }
 
 }  // namespace x87

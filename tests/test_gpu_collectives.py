@@ -15,6 +15,7 @@ import pytest
 from oracle import oracle as O
 from sos_amd import _lib, shmem as S
 
+import ldbl_vectors as V
 import plansim
 
 pytestmark = pytest.mark.gpu
@@ -116,11 +117,11 @@ def test_prefix_kernel_aliasing(torch_cuda, np_, op):
 
 @pytest.mark.parametrize("P", [9, 12, 16, 64])
 @pytest.mark.parametrize("order", [0, 1])
-@pytest.mark.parametrize("dt,op", [(23, 5), (11, 2), (27, 6), (4, 4)])
+@pytest.mark.parametrize("dt,op", [(23, 5), (11, 2), (27, 6), (4, 4), (25, 5)])
 def test_fold_runtime_p(torch_cuda, P, order, dt, op):
     torch = torch_cuda
     n = 1001
-    ins = [O.fill(dt, 1 if op == 6 else 0, 3, k, n) for k in range(P)]
+    ins = fold_inputs(dt, op, P, n, 3)
     ref = plansim.fold_values(op, dt, ins, order)
     di = [to_dev(torch, a) for a in ins]
     out = torch.zeros_like(di[0])
@@ -131,7 +132,7 @@ def test_fold_runtime_p(torch_cuda, P, order, dt, op):
 
 @pytest.mark.parametrize("P", [2, 3, 4, 5, 6, 7, 8])
 @pytest.mark.parametrize("order", [0, 1])
-@pytest.mark.parametrize("dt,op", [(23, 5), (24, 4), (11, 2), (27, 6), (26, 5), (3, 3)])
+@pytest.mark.parametrize("dt,op", [(23, 5), (24, 4), (11, 2), (27, 6), (26, 5), (3, 3), (25, 5)])
 def test_fold_small_inputs(torch_cuda, P, order, dt, op):
     """Folds of inputs of at most 64 KiB each (k_fold_dyn, the latency-bound path of the
     small team calls): every input's element is loaded before the first combine; the
@@ -140,7 +141,7 @@ def test_fold_small_inputs(torch_cuda, P, order, dt, op):
     torch = torch_cuda
     es = O.lib().oracle_type_size(dt)
     for n in (1, 7, 1000, (1 << 16) // es):
-        ins = [O.fill(dt, 1 if op == 6 else 0, 17, k, n) for k in range(P)]
+        ins = fold_inputs(dt, op, P, n, 17)
         ref = plansim.fold_values(op, dt, ins, order)
         for off in (0, es if es < 16 else 0):
             di = [to_dev(torch, a, off) for a in ins]
@@ -343,7 +344,8 @@ def test_gather_dpp_shape_forced():
 
 def _perspective_inputs(dt, P, n, seed):
     """Inputs whose recdbl_sw value depends on the PE: fp +-0 ties and NaNs with a
-    distinct payload per PE (x86 keeps the first NaN operand), next to ordinary values."""
+    distinct payload per PE (SSE keeps the first NaN operand, the x87 chooses by
+    significand and sign), next to ordinary values."""
     srcs = [src_of(dt, seed, p, n) for p in range(P)]
     if dt in (23, 24):
         ity = np.uint32 if dt == 23 else np.uint64
@@ -352,7 +354,26 @@ def _perspective_inputs(dt, P, n, seed):
             s = srcs[p]
             s[0] = -0.0 if p % 2 else 0.0
             s.view(ity)[min(1, n - 1)] = nan0 | ity(p + 1)
+    if dt == 25:
+        # x87 keeps the NaN whose stored significand is larger, on equal ones the positive:
+        # quiet NaNs on the even PEs, signalling ones with larger payloads on the odd PEs,
+        # the sign alternating in threes; then one significand on every PE, signs mixed
+        for p in range(P):
+            rows = srcs[p].view(np.uint8).reshape(-1, 16)
+            rows[0, :10] = np.frombuffer(V.encode(p % 2, 0, 0)[:10], np.uint8)
+            m = (0x8000000000000100 if p % 2 else 0xC000000000000000) | (p + 1)
+            rows[min(1, n - 1), :10] = np.frombuffer(V.encode(p % 3 == 2, 0x7FFF, m)[:10], np.uint8)
+            if n > 2:
+                rows[2, :10] = np.frombuffer(V.encode((p + 1) % 2, 0x7FFF, 0xC000000000000007)[:10], np.uint8)
+            rows[:, 10:] = 0x10 + p
     return srcs
+
+
+def fold_inputs(dt, op, P, n, seed):
+    """The fold tests' inputs: the oracle's generator, for long double per-PE specials."""
+    if dt == 25:
+        return _perspective_inputs(dt, P, n, seed)
+    return [O.fill(dt, 1 if op == 6 else 0, seed, k, n) for k in range(P)]
 
 
 def _pinned(torch, raw, offset):
