@@ -139,6 +139,20 @@ def c11_generic(name, arms, argidx=1):
     return out
 
 
+def c11_prelude(guarded=True):
+    """The helper macros of the C11 selectors.  shmem_reductions.h defines them
+    unconditionally; the headers that may come after it guard them."""
+    out = ["#define SHMEM_C11_TYPE_EVAL_PTR(arg) &*(arg)",
+           "#define SHMEM_C11_ARG1(first, ...) SHMEM_C11_ARG1_HELPER(__VA_ARGS__, sentinel)",
+           "#define SHMEM_C11_ARG1_HELPER(second, ...) second"]
+    return ["#ifndef SHMEM_C11_TYPE_EVAL_PTR"] + out + ["#endif"] if guarded else out
+
+
+def definition(out, sig, name, body):
+    """One entry point: the strong pshmem form with its one-line body, the weak alias."""
+    out += [sig("p"), "{", f"    {body}", "}", f"{sig('')} __attribute__((weak, alias(\"p{name}\")));", ""]
+
+
 def scan_header():
     out = ["/* shmemx_scans.h -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.",
            " *",
@@ -159,11 +173,7 @@ def scan_header():
                        f"const {ct} *source, size_t nelems) {{ return shmemx_{st}_sum_{k}(team, "
                        f"dest, source, nelems); }}")
     out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
-    out.append("#ifndef SHMEM_C11_TYPE_EVAL_PTR")
-    out.append("#define SHMEM_C11_TYPE_EVAL_PTR(arg) &*(arg)")
-    out.append("#define SHMEM_C11_ARG1(first, ...) SHMEM_C11_ARG1_HELPER(__VA_ARGS__, sentinel)")
-    out.append("#define SHMEM_C11_ARG1_HELPER(second, ...) second")
-    out.append("#endif")
+    out += c11_prelude()
     for k in ("exscan", "inscan"):
         out += c11_generic(f"shmemx_sum_{k}",
                            [f"        {ct}*: shmemx_{st}_sum_{k}" for st, ct in GENERIC_TABLE["sum"]])
@@ -214,15 +224,10 @@ def header():
                    f"nelems, PE_root); }}")
     # C11 generics
     out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
-    out.append("#define SHMEM_C11_TYPE_EVAL_PTR(arg) &*(arg)")
-    out.append("#define SHMEM_C11_ARG1(first, ...) SHMEM_C11_ARG1_HELPER(__VA_ARGS__, sentinel)")
-    out.append("#define SHMEM_C11_ARG1_HELPER(second, ...) second")
+    out += c11_prelude(guarded=False)
     for op in ("and", "or", "xor", "min", "max", "sum", "prod"):
-        arms = [f"        {ct}*: shmem_{st}_{op}_reduce" for st, ct in GENERIC_TABLE[op]]
-        out.append(f"#define shmem_{op}_reduce(...) \\")
-        out.append("    _Generic(SHMEM_C11_TYPE_EVAL_PTR(SHMEM_C11_ARG1(__VA_ARGS__)), \\")
-        out.append(", \\\n".join(arms) + " \\")
-        out.append("    )(__VA_ARGS__)")
+        out += c11_generic(f"shmem_{op}_reduce",
+                           [f"        {ct}*: shmem_{st}_{op}_reduce" for st, ct in GENERIC_TABLE[op]])
     out += c11_generic("shmem_broadcast", [f"        {ct}*: shmem_{st}_broadcast" for st, ct in GENERIC_RMA])
     out.append("#endif")
     out += ["", "#endif /* SHMEM_REDUCTIONS_H */", ""]
@@ -240,40 +245,24 @@ def source():
            'extern "C" {', ""]
     for (st, ct, it), op in TO_ALL:
         name = f"shmem_{st}_{op}_to_all"
-        out.append(f"{to_all_sig('p', st, ct, op)}")
-        out.append("{")
-        out.append(f"    sos_api_to_all(target, source, nreduce, sizeof({ct}), PE_start, logPE_stride, "
+        definition(out, lambda p: to_all_sig(p, st, ct, op), name,
+                   f"sos_api_to_all(target, source, nreduce, sizeof({ct}), PE_start, logPE_stride, "
                    f"PE_size, pWrk, pSync, SOSX_OP_{OPS[op]}, SOSX_DT_{it}, \"{name}\");")
-        out.append("}")
-        out.append(f"{to_all_sig('', st, ct, op)} __attribute__((weak, alias(\"p{name}\")));")
-        out.append("")
     for (st, ct, it), op in REDUCE:
         name = f"shmem_{st}_{op}_reduce"
-        out.append(f"{reduce_sig('p', st, ct, op)}")
-        out.append("{")
-        out.append(f"    return sos_api_reduce(team, dest, source, nreduce, sizeof({ct}), "
+        definition(out, lambda p: reduce_sig(p, st, ct, op), name,
+                   f"return sos_api_reduce(team, dest, source, nreduce, sizeof({ct}), "
                    f"SOSX_OP_{OPS[op]}, SOSX_DT_{it}, \"{name}\");")
-        out.append("}")
-        out.append(f"{reduce_sig('', st, ct, op)} __attribute__((weak, alias(\"p{name}\")));")
-        out.append("")
     for st, ct in RMA:
         name = f"shmem_{st}_broadcast"
-        out.append(f"{bcast_sig('p', st, ct)}")
-        out.append("{")
-        out.append(f"    return sos_api_broadcast(team, dest, source, nelems, sizeof({ct}), PE_root, "
+        definition(out, lambda p: bcast_sig(p, st, ct), name,
+                   f"return sos_api_broadcast(team, dest, source, nelems, sizeof({ct}), PE_root, "
                    f"\"{name}\");")
-        out.append("}")
-        out.append(f"{bcast_sig('', st, ct)} __attribute__((weak, alias(\"p{name}\")));")
-        out.append("")
     for (st, ct, it), k in SCANS:
         name = f"shmemx_{st}_sum_{k}"
-        out.append(f"{scan_sig('p', st, ct, k)}")
-        out.append("{")
-        out.append(f"    return sos_api_scan(team, dest, source, nelems, sizeof({ct}), SOSX_OP_SUM, "
+        definition(out, lambda p: scan_sig(p, st, ct, k), name,
+                   f"return sos_api_scan(team, dest, source, nelems, sizeof({ct}), SOSX_OP_SUM, "
                    f"SOSX_DT_{it}, {1 if k == 'exscan' else 0}, \"{name}\");")
-        out.append("}")
-        out.append(f"{scan_sig('', st, ct, k)} __attribute__((weak, alias(\"p{name}\")));")
-        out.append("")
     out += ['}  // extern "C"', ""]
     return "\n".join(out)
 
@@ -296,73 +285,90 @@ def collect_mem_sig(prefix, kind):
 
 
 def collect_active_sig(prefix, kind, bits):
-    first = "void *target, const void *source, size_t nlong" if kind == "fcollect" else (
+    first = "void *target, const void *source, size_t nlong" if kind in ("fcollect", "collect") else (
         f"void *dest, const void *source, {_STRIDES[kind]}size_t nelems")
     return (f"void {prefix}shmem_{kind}{bits}({first}, int PE_start, int logPE_stride, int PE_size, "
             f"long *pSync)")
 
 
-def collects_header():
-    out = ["/* shmem_collects.h -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.",
-           " *",
-           " * SOS's fcollect, alltoall and alltoalls: the 72 typed team forms",
-           " * shmem_<T>_{fcollect,alltoall,alltoalls} (src/collectives_c.c4:536-707), the",
-           " * three mem forms, the six deprecated active-set forms, the C11 generic selectors",
-           " * and the C++ overloads.  Included from shmem.h. */",
-           "#ifndef SHMEM_COLLECTS_H", "#define SHMEM_COLLECTS_H", "",
-           "#ifdef __cplusplus", 'extern "C" {', "#endif", ""]
-    for kind in COLLECTS:
-        for st, ct in RMA:
-            out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_sig('', st, ct, kind)};")
-        out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_mem_sig('', kind)};")
-        for bits in (32, 64):
-            out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_active_sig('', kind, bits)};")
-        out.append("")
-    out.append("/* profiling interface: pshmem_* are the implementations, shmem_* weak aliases */")
-    for kind in COLLECTS:
-        for st, ct in RMA:
-            out.append(f"{collect_sig('p', st, ct, kind)};")
-        out.append(f"{collect_mem_sig('p', kind)};")
-        for bits in (32, 64):
-            out.append(f"{collect_active_sig('p', kind, bits)};")
+# The two generated families over the RMA table: a header and a source each.  `untyped_here`:
+# the source also defines the mem and active-set forms (the collects' are written by hand).
+# collect (variable lengths: SHMEM_BIND_C_RMA of SHMEM_DEF_COLLECT, shmem_collectmem and the
+# deprecated shmem_collect32/64, src/collectives_c.c4:432-503) has files of its own.
+FAMILIES = {
+    "collects": dict(
+        kinds=COLLECTS, header="shmem_collects.h", source="collects_gen.cpp", untyped_here=False,
+        about_header=[" * SOS's fcollect, alltoall and alltoalls: the 72 typed team forms",
+                      " * shmem_<T>_{fcollect,alltoall,alltoalls} (src/collectives_c.c4:536-707), the",
+                      " * three mem forms, the six deprecated active-set forms, the C11 generic selectors",
+                      " * and the C++ overloads.  Included from shmem.h. */"],
+        about_source=["// The 72 typed fcollect / alltoall / alltoalls entry points (SHMEM_DEF_FCOLLECT,",
+                      "// SHMEM_DEF_ALLTOALL, SHMEM_DEF_ALLTOALLS over SHMEM_BIND_C_RMA,",
+                      "// src/collectives_c.c4:536-707): strong pshmem_*, weak shmem_* aliases."]),
+    "collectv": dict(
+        kinds=("collect",), header="shmem_collectv.h", source="collectv_gen.cpp", untyped_here=True,
+        about_header=[" * SOS's collect (concatenation of per-PE contributions of different lengths): the",
+                      " * 24 typed team forms shmem_<T>_collect (src/collectives_c.c4:463-485),",
+                      " * shmem_collectmem, the deprecated active-set shmem_collect32/64, the C11 generic",
+                      " * selector and the C++ overloads.  Included from shmem.h. */"],
+        about_source=["// The 24 typed collect entry points (SHMEM_DEF_COLLECT over SHMEM_BIND_C_RMA),",
+                      "// shmem_collectmem and the active-set shmem_collect32/64",
+                      "// (src/collectives_c.c4:432-503): strong pshmem_*, weak shmem_* aliases."]),
+}
+
+
+def family_header(fam):
+    guard = fam["header"].upper().replace(".", "_")
+    out = [f"/* {fam['header']} -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", " *"]
+    out += fam["about_header"]
+    out += [f"#ifndef {guard}", f"#define {guard}", "", "#ifdef __cplusplus", 'extern "C" {', "#endif", ""]
+    for attr, prefix in (("SHMEM_FUNCTION_ATTRIBUTES ", ""), ("", "p")):
+        if prefix:
+            out.append("/* profiling interface: pshmem_* are the implementations, shmem_* weak aliases */")
+        for kind in fam["kinds"]:
+            for st, ct in RMA:
+                out.append(f"{attr}{collect_sig(prefix, st, ct, kind)};")
+            out.append(f"{attr}{collect_mem_sig(prefix, kind)};")
+            for bits in (32, 64):
+                out.append(f"{attr}{collect_active_sig(prefix, kind, bits)};")
+            if not prefix:
+                out.append("")
     out += ["", "#ifdef __cplusplus", "}  /* extern \"C\" */", "#endif", ""]
     out.append("#if defined(__cplusplus)")
-    for kind in COLLECTS:
+    for kind in fam["kinds"]:
         for st, ct in GENERIC_RMA:
             out.append(f"static inline int shmem_{kind}(shmem_team_t team, {ct} *dest, const {ct} *source, "
                        f"{_STRIDES[kind]}size_t nelems) {{ return shmem_{st}_{kind}(team, dest, source, "
                        f"{_STRIDE_ARGS[kind]}nelems); }}")
     out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
-    out.append("#ifndef SHMEM_C11_TYPE_EVAL_PTR")
-    out.append("#define SHMEM_C11_TYPE_EVAL_PTR(arg) &*(arg)")
-    out.append("#define SHMEM_C11_ARG1(first, ...) SHMEM_C11_ARG1_HELPER(__VA_ARGS__, sentinel)")
-    out.append("#define SHMEM_C11_ARG1_HELPER(second, ...) second")
-    out.append("#endif")
-    for kind in COLLECTS:
+    out += c11_prelude()
+    for kind in fam["kinds"]:
         out += c11_generic(f"shmem_{kind}", [f"        {ct}*: shmem_{st}_{kind}" for st, ct in GENERIC_RMA])
     out.append("#endif")
-    out += ["", "#endif /* SHMEM_COLLECTS_H */", ""]
+    out += ["", f"#endif /* {guard} */", ""]
     return "\n".join(out)
 
 
-def collects_source():
-    out = ["// collects_gen.cpp -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.",
-           "//",
-           "// The 72 typed fcollect / alltoall / alltoalls entry points (SHMEM_DEF_FCOLLECT,",
-           "// SHMEM_DEF_ALLTOALL, SHMEM_DEF_ALLTOALLS over SHMEM_BIND_C_RMA,",
-           "// src/collectives_c.c4:536-707): strong pshmem_*, weak shmem_* aliases.",
-           '#include "shmem.h"', '#include "api_internal.h"', "",
-           'extern "C" {', ""]
-    for kind in COLLECTS:
+def family_source(fam):
+    out = [f"// {fam['source']} -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", "//"]
+    out += fam["about_source"]
+    out += ['#include "shmem.h"', '#include "api_internal.h"', "", 'extern "C" {', ""]
+    for kind in fam["kinds"]:
         for st, ct in RMA:
             name = f"shmem_{st}_{kind}"
-            out.append(f"{collect_sig('p', st, ct, kind)}")
-            out.append("{")
-            out.append(f"    return sos_api_{kind}(team, dest, source, {_STRIDE_ARGS[kind]}nelems, "
+            definition(out, lambda p: collect_sig(p, st, ct, kind), name,
+                       f"return sos_api_{kind}(team, dest, source, {_STRIDE_ARGS[kind]}nelems, "
                        f"sizeof({ct}), \"{name}\");")
-            out.append("}")
-            out.append(f"{collect_sig('', st, ct, kind)} __attribute__((weak, alias(\"p{name}\")));")
-            out.append("")
+        if not fam["untyped_here"]:
+            continue
+        name = f"shmem_{kind}mem"
+        definition(out, lambda p: collect_mem_sig(p, kind), name,
+                   f"return sos_api_{kind}(team, dest, source, {_STRIDE_ARGS[kind]}nelems, 1, \"{name}\");")
+        for bits in (32, 64):
+            name = f"shmem_{kind}{bits}"
+            definition(out, lambda p: collect_active_sig(p, kind, bits), name,
+                       f"sos_api_{kind}_active(target, source, nlong, {bits // 8}, PE_start, logPE_stride, "
+                       f"PE_size, pSync, \"{name}\");")
     out += ['}  // extern "C"', ""]
     return "\n".join(out)
 
@@ -370,87 +376,6 @@ def collects_source():
 def collect_symbols():
     """The generated fcollect / alltoall / alltoalls names (typed forms only)."""
     return [f"shmem_{st}_{kind}" for kind in COLLECTS for st, ct in RMA]
-
-
-# collect (variable lengths) over the RMA table: SHMEM_BIND_C_RMA of SHMEM_DEF_COLLECT, plus
-# shmem_collectmem and the deprecated shmem_collect32/64 (src/collectives_c.c4:432-503).
-# Files of their own, beside shmem_collects.h / collects_gen.cpp.
-def collectv_active_sig(prefix, bits):
-    return (f"void {prefix}shmem_collect{bits}(void *target, const void *source, size_t nlong, "
-            f"int PE_start, int logPE_stride, int PE_size, long *pSync)")
-
-
-def collectv_header():
-    out = ["/* shmem_collectv.h -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.",
-           " *",
-           " * SOS's collect (concatenation of per-PE contributions of different lengths): the",
-           " * 24 typed team forms shmem_<T>_collect (src/collectives_c.c4:463-485),",
-           " * shmem_collectmem, the deprecated active-set shmem_collect32/64, the C11 generic",
-           " * selector and the C++ overloads.  Included from shmem.h. */",
-           "#ifndef SHMEM_COLLECTV_H", "#define SHMEM_COLLECTV_H", "",
-           "#ifdef __cplusplus", 'extern "C" {', "#endif", ""]
-    for st, ct in RMA:
-        out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_sig('', st, ct, 'collect')};")
-    out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collect_mem_sig('', 'collect')};")
-    for bits in (32, 64):
-        out.append(f"SHMEM_FUNCTION_ATTRIBUTES {collectv_active_sig('', bits)};")
-    out.append("")
-    out.append("/* profiling interface: pshmem_* are the implementations, shmem_* weak aliases */")
-    for st, ct in RMA:
-        out.append(f"{collect_sig('p', st, ct, 'collect')};")
-    out.append(f"{collect_mem_sig('p', 'collect')};")
-    for bits in (32, 64):
-        out.append(f"{collectv_active_sig('p', bits)};")
-    out += ["", "#ifdef __cplusplus", "}  /* extern \"C\" */", "#endif", ""]
-    out.append("#if defined(__cplusplus)")
-    for st, ct in GENERIC_RMA:
-        out.append(f"static inline int shmem_collect(shmem_team_t team, {ct} *dest, const {ct} *source, "
-                   f"size_t nelems) {{ return shmem_{st}_collect(team, dest, source, nelems); }}")
-    out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
-    out.append("#ifndef SHMEM_C11_TYPE_EVAL_PTR")
-    out.append("#define SHMEM_C11_TYPE_EVAL_PTR(arg) &*(arg)")
-    out.append("#define SHMEM_C11_ARG1(first, ...) SHMEM_C11_ARG1_HELPER(__VA_ARGS__, sentinel)")
-    out.append("#define SHMEM_C11_ARG1_HELPER(second, ...) second")
-    out.append("#endif")
-    out += c11_generic("shmem_collect", [f"        {ct}*: shmem_{st}_collect" for st, ct in GENERIC_RMA])
-    out.append("#endif")
-    out += ["", "#endif /* SHMEM_COLLECTV_H */", ""]
-    return "\n".join(out)
-
-
-def collectv_source():
-    out = ["// collectv_gen.cpp -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.",
-           "//",
-           "// The 24 typed collect entry points (SHMEM_DEF_COLLECT over SHMEM_BIND_C_RMA),",
-           "// shmem_collectmem and the active-set shmem_collect32/64",
-           "// (src/collectives_c.c4:432-503): strong pshmem_*, weak shmem_* aliases.",
-           '#include "shmem.h"', '#include "api_internal.h"', "",
-           'extern "C" {', ""]
-    for st, ct in RMA:
-        name = f"shmem_{st}_collect"
-        out.append(f"{collect_sig('p', st, ct, 'collect')}")
-        out.append("{")
-        out.append(f"    return sos_api_collect(team, dest, source, nelems, sizeof({ct}), \"{name}\");")
-        out.append("}")
-        out.append(f"{collect_sig('', st, ct, 'collect')} __attribute__((weak, alias(\"p{name}\")));")
-        out.append("")
-    out.append(f"{collect_mem_sig('p', 'collect')}")
-    out.append("{")
-    out.append('    return sos_api_collect(team, dest, source, nelems, 1, "shmem_collectmem");')
-    out.append("}")
-    out.append(f"{collect_mem_sig('', 'collect')} __attribute__((weak, alias(\"pshmem_collectmem\")));")
-    out.append("")
-    for bits in (32, 64):
-        name = f"shmem_collect{bits}"
-        out.append(f"{collectv_active_sig('p', bits)}")
-        out.append("{")
-        out.append(f"    sos_api_collect_active(target, source, nlong, {bits // 8}, PE_start, logPE_stride, "
-                   f"PE_size, pSync, \"{name}\");")
-        out.append("}")
-        out.append(f"{collectv_active_sig('', bits)} __attribute__((weak, alias(\"p{name}\")));")
-        out.append("")
-    out += ['}  // extern "C"', ""]
-    return "\n".join(out)
 
 
 def collectv_symbols():
@@ -472,11 +397,10 @@ def main():
     assert len(RMA) == 24 and len(SCANS) == 52, (len(RMA), len(SCANS))
     targets = {os.path.join(ROOT, "include", "shmem_reductions.h"): header(),
                os.path.join(ROOT, "include", "shmemx_scans.h"): scan_header(),
-               os.path.join(ROOT, "sos_amd", "csrc", "reductions_gen.cpp"): source(),
-               os.path.join(ROOT, "include", "shmem_collects.h"): collects_header(),
-               os.path.join(ROOT, "sos_amd", "csrc", "collects_gen.cpp"): collects_source(),
-               os.path.join(ROOT, "include", "shmem_collectv.h"): collectv_header(),
-               os.path.join(ROOT, "sos_amd", "csrc", "collectv_gen.cpp"): collectv_source()}
+               os.path.join(ROOT, "sos_amd", "csrc", "reductions_gen.cpp"): source()}
+    for fam in FAMILIES.values():
+        targets[os.path.join(ROOT, "include", fam["header"])] = family_header(fam)
+        targets[os.path.join(ROOT, "sos_amd", "csrc", fam["source"])] = family_source(fam)
     check = "--check" in sys.argv
     stale = False
     for path, text in targets.items():

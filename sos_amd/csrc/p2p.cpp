@@ -54,6 +54,8 @@
 #include <vector>
 
 #include "carry.h"
+#include "executor.h"
+#include "hostwait.h"
 #include "p2p_proto.h"
 #include "plan.h"
 #include "runtime.h"
@@ -65,8 +67,6 @@ extern "C" int sosx_gather(int nseg, const void *const *srcs, void *const *dsts,
                            const size_t *bytes, void *stream);
 
 namespace sosrt {
-
-void prof_mark(int which, bool end, hipStream_t s);  // collectives.cpp (0 = fold, 1 = transfer)
 
 namespace {
 
@@ -97,8 +97,6 @@ template <class X> X *dev(X *host)
     return (X *)(g_sig.dbase + ((char *)host - (char *)shared()));
 }
 
-// Wall-clock bound of one wait (SHMEMX_P2P_TIMEOUT seconds, default 300): a peer that
-// never posts ends the job with a message instead of hanging it.
 // Test hook (tests/test_gpu_multipe.py::test_p2p_stall_mid_call): the PE named by
 // SOSX_P2P_TEST_STALL_PE stops for 60 s right after the entry boundary of its first
 // multi-round call, so its peers meet the bounded DEVICE waits of the later rounds.
@@ -135,60 +133,22 @@ hipError_t complete(hipStream_t stream)
     return sync_system(stream);
 }
 
-double wait_limit_s()
+// Wait until load() (an acquire load of a pair counter) reaches `want`: 4096 pauses, then
+// yield between polls, the clock every 1024 of those.
+template <class Load> void wait_counter(Load load, uint64_t want, const char *what)
 {
-    static const double lim = [] {
-        const char *e = getenv("SHMEMX_P2P_TIMEOUT");
-        const double v = e ? atof(e) : 0.0;
-        return v > 0 ? v : 300.0;
-    }();
-    return lim;
-}
-
-double now_s()
-{
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
-void spin_until(std::atomic<uint64_t> &a, uint64_t want, const char *what)
-{
-    unsigned spins = 0;
-    double t0 = 0;
-    while (a.load(std::memory_order_acquire) < want) {
-        if (++spins < 4096) {
-            __builtin_ia32_pause();
-            continue;
-        }
-        sched_yield();
-        if ((spins & 1023) == 0) {
-            const double t = now_s();
-            if (t0 == 0) t0 = t;
-            else if (t - t0 > wait_limit_s())
-                raise_error("p2p transport: timed out after %.0f s waiting for %s", t - t0, what);
-        }
-    }
-}
-
-// The same bound for a counter the GPUs also write (stream mode).
-void spin_until_u64(const uint64_t *a, uint64_t want, const char *what)
-{
-    unsigned spins = 0;
-    double t0 = 0;
-    while (__atomic_load_n(a, __ATOMIC_ACQUIRE) < want) {
-        if (++spins < 4096) {
-            __builtin_ia32_pause();
-            continue;
-        }
-        sched_yield();
-        if ((spins & 1023) == 0) {
-            const double t = now_s();
-            if (t0 == 0) t0 = t;
-            else if (t - t0 > wait_limit_s())
-                raise_error("p2p transport: timed out after %.0f s waiting for %s", t - t0, what);
-        }
-    }
+    spin_until([&] { return load() >= want; },
+               [](unsigned spins) {
+                   if (spins < 4096) {
+                       __builtin_ia32_pause();
+                       return false;
+                   }
+                   sched_yield();
+                   return (spins & 1023) == 0;
+               },
+               [&](double waited) {
+                   raise_error("p2p transport: timed out after %.0f s waiting for %s", waited, what);
+               });
 }
 
 // SOSX_P2P_TRACE=N (diagnostics): host time per phase of p2p_exec, averaged and printed
@@ -534,12 +494,12 @@ struct HipBackend {
     const char *peer_base(int pw) { return st().peer_heap[(size_t)pw]; }
     void spin(std::atomic<uint64_t> &a, uint64_t want, const char *what)
     {
-        spin_until(a, want, what);
+        wait_counter([&] { return a.load(std::memory_order_acquire); }, want, what);
         if (sosp2p::in_posted(shared(), &a)) note_peer_wait();
     }
-    void spin_u64(const uint64_t *a, uint64_t want, const char *what)
+    void spin_u64(const uint64_t *a, uint64_t want, const char *what)  // the GPUs write it too
     {
-        spin_until_u64(a, want, what);
+        wait_counter([&] { return __atomic_load_n(a, __ATOMIC_ACQUIRE); }, want, what);
         if (sosp2p::in_dposted(shared(), (const char *)shared(), a)) note_peer_wait();
     }
     void entry_hook() { stall_hook(); }

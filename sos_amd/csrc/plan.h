@@ -35,7 +35,7 @@
 //                 own copy, then one direct allgather inside DST.
 //   ALLTOALL      block q of the source to PE q (src/collectives.c:1449-1480): one direct
 //                 exchange round, then the self block.  alltoalls runs this plan over
-//                 packed operands (collectives.cpp).
+//                 packed operands (api.cpp).
 //   COLLECT       every PE's contribution of its OWN length in PE order
 //                 (src/collectives.c:1215-1276): the own copy to the exclusive prefix of
 //                 the lengths, then one direct uneven allgather inside DST.  The only plan
@@ -75,6 +75,8 @@ inline bool is_bcast(int alg) { return alg >= PLAN_BCAST; }
 inline bool is_fcollect(int alg) { return alg == PLAN_FCOLLECT; }
 inline bool is_alltoall(int alg) { return alg == PLAN_ALLTOALL; }
 inline bool is_collect(int alg) { return alg == PLAN_COLLECT; }
+// Never runs in place: blocks arrive in the target while peers still read the source.
+inline bool never_in_place(int alg) { return is_fcollect(alg) || is_alltoall(alg) || is_collect(alg); }
 inline int bcast_alg(int root, bool copy_root) { return PLAN_BCAST + 2 * root + (copy_root ? 1 : 0); }
 
 struct Xfer {

@@ -81,7 +81,7 @@ struct State {
     void *stage = nullptr;            // staging for host-resident source/target
     size_t stage_bytes = 0;
     int *dbar = nullptr;              // 1-int device word for barriers
-    // host-resident ring reductions, pipelined in stripes (collectives.cpp): copy streams,
+    // host-resident ring reductions, pipelined in stripes (executor.cpp): copy streams,
     // per-slot events, three device stripe slots (the RCCL path's; p2p uses the stage)
     hipStream_t pipe_h2d = nullptr, pipe_d2h = nullptr;
     hipEvent_t pipe_ev[3][3] = {};    // [slot][h2d done, exchange done, d2h done]
@@ -92,7 +92,7 @@ struct State {
     long acquire_kernels = 0;         // of sys_acquires: stream-wide acquire kernels
     bool acq_pending = false;         // a peer wait since the last acquire (stream order)
     unsigned *acq_mask = nullptr;     // device word: XCD ids the acquire kernels ran on
-    uint64_t *collect_lens = nullptr; // pinned: collect's internal lengths fcollect (collectives.cpp)
+    uint64_t *collect_lens = nullptr; // pinned: collect's internal lengths fcollect (api.cpp)
     void *stripes = nullptr;
     size_t stripes_bytes = 0;
     size_t host_stripe_bytes = 256u << 10; // SHMEMX_HOST_STRIPE_BYTES: min slice (0 = off)

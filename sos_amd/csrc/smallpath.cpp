@@ -54,7 +54,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 #include <atomic>
@@ -62,6 +61,7 @@
 #include <map>
 #include <vector>
 
+#include "hostwait.h"
 #include "plan.h"
 #include "runtime.h"
 #include "sosx.h"
@@ -150,31 +150,18 @@ SmallCtl *ctl(int pe) { return (SmallCtl *)(g.host + (size_t)pe * sizeof(SmallCt
 
 size_t slot_off(int pe, int sl) { return ctl_bytes(g.npes) + ((size_t)pe * 2 + (size_t)sl) * g.slot; }
 
-double limit_s()
-{
-    const char *e = getenv("SHMEMX_P2P_TIMEOUT");
-    const double v = e ? atof(e) : 0.0;
-    return v > 0 ? v : 300.0;
-}
-
-double now_s()
-{
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
+// The waits of this path pause between polls and never yield; the clock every 65536 polls.
 void wait_ge(const std::atomic<uint64_t> &w, uint64_t v, const char *what)
 {
-    if (w.load(std::memory_order_acquire) >= v) return;
-    const double t0 = now_s();
-    unsigned spins = 0;
-    while (w.load(std::memory_order_acquire) < v) {
-        __builtin_ia32_pause();
-        if ((++spins & 0xFFFF) == 0 && now_s() - t0 > limit_s())
-            raise_error("small shared-memory path: timed out after %.0f s waiting for %s",
-                        limit_s(), what);
-    }
+    spin_until([&] { return w.load(std::memory_order_acquire) >= v; },
+               [](unsigned spins) {
+                   __builtin_ia32_pause();
+                   return (spins & 0xFFFF) == 0;
+               },
+               [&](double) {
+                   raise_error("small shared-memory path: timed out after %.0f s waiting for %s",
+                               wait_limit_s(), what);
+               });
 }
 
 // Wait until workgroups [0, nb) of the small fold stored `seq`.  The host polls pinned
@@ -204,8 +191,8 @@ void wait_flags(const uint32_t *flags, int nb, uint32_t seq, const char *fn)
             return;
         }
         if (e != hipErrorNotReady) hip_check(e, fn);
-        if (now_s() - t0 > limit_s())
-            raise_error("%s: small shared-memory path: timed out after %.0f s", fn, limit_s());
+        if (now_s() - t0 > wait_limit_s())
+            raise_error("%s: small shared-memory path: timed out after %.0f s", fn, wait_limit_s());
     }
 }
 
@@ -403,18 +390,72 @@ void wait_post(int q, uint64_t kp, uint64_t mine, const char *fn)
 {
     const int mw = st().my_pe;
     const std::atomic<uint64_t> &w = ctl(q)->posted[mw].v;
-    if (w.load(std::memory_order_acquire) >= kp) return;
-    const double t0 = now_s();
     double past = 0;
-    unsigned spins = 0;
-    while (w.load(std::memory_order_acquire) < kp) {
-        __builtin_ia32_pause();
-        if ((++spins & 0xFF) != 0) continue;
-        route_check(q, kp, mine, fn, past);
-        if ((spins & 0xFFFF) == 0 && now_s() - t0 > limit_s())
-            raise_error("small shared-memory path: timed out after %.0f s waiting for a peer's operand",
-                        limit_s());
+    spin_until([&] { return w.load(std::memory_order_acquire) >= kp; },
+               [&](unsigned spins) {  // the route words every 256 polls
+                   __builtin_ia32_pause();
+                   if ((spins & 0xFF) != 0) return false;
+                   route_check(q, kp, mine, fn, past);
+                   return (spins & 0xFFFF) == 0;
+               },
+               [](double) {
+                   raise_error("small shared-memory path: timed out after %.0f s waiting for a peer's operand",
+                               wait_limit_s());
+               });
+}
+
+// ---- the slot protocol (file comment, "Slot reuse"), written once for the reductions and
+// ---- collect; taking the peers' posts stays with each caller (how it waits differs)
+
+// Claim my next data slot: free once every receiver of its previous post has read it.
+int claim_slot()
+{
+    const int mw = st().my_pe;
+    const int sl = (int)(g.seq++ % 2);
+    for (const auto &u : g.slot_users[sl]) wait_ge(ctl(u.first)->consumed[mw].v, u.second, "a peer to read a slot");
+    g.slot_users[sl].clear();
+    return sl;
+}
+
+// Publish my slot sl, filled by the host, to every other member of t: the slot id, then
+// the post.  `staged`: a device source instead reaches the slot (at `payload_off`) through
+// a one-workgroup copy launch that then makes the posts itself (sosx_small_stage), so the
+// host goes straight on to the peers' posts and later launches queue behind the copy.
+void post_slot(const Team &t, int sl, bool staged, size_t payload_off, const void *source, size_t bytes,
+               const char *fn)
+{
+    const int mw = st().my_pe;
+    std::atomic_thread_fence(std::memory_order_release);
+    SmallCtl *mine = ctl(mw);
+    uint64_t *words[kMaxPE];
+    uint64_t vals[kMaxPE];
+    int nw = 0;
+    for (int i = 0; i < t.size; ++i) {
+        if (i == t.my_idx) continue;
+        const int r = t.world_rank(i);
+        const uint64_t k = ++g.posted_to[r];
+        mine->ring[r][k % 2] = (uint32_t)sl;
+        if (staged) {  // the copy kernel's post: the device view of the same word
+            words[nw] = (uint64_t *)(g.dev + ((char *)&mine->posted[r].v - g.host));
+            vals[nw++] = k;
+        } else {
+            mine->posted[r].v.store(k, std::memory_order_release);
+        }
+        g.slot_users[sl].push_back({r, k});
     }
+    if (!staged) return;
+    std::atomic_thread_fence(std::memory_order_seq_cst);  // what the host wrote before the launch
+    const int rc = sosx_small_stage(g.dev + slot_off(mw, sl) + payload_off, source, bytes, words, vals, nw,
+                                    st().stream);
+    if (rc) raise_error("%s: small-path copy of a device operand failed (status %d)", fn, rc);
+}
+
+// The launch has read the slots taken from from[0, n) (world PEs; -1: none): acknowledge.
+void ack_slots(const int *from, int n)
+{
+    SmallCtl *mine = ctl(st().my_pe);
+    for (int i = 0; i < n; ++i)
+        if (from[i] >= 0) mine->consumed[from[i]].v.store(g.seen_from[from[i]], std::memory_order_release);
 }
 
 }  // namespace
@@ -458,7 +499,6 @@ void small_path_reduce(int alg, void *target, const void *source, size_t count, 
     State &s = st();
     const size_t bytes = count * ts;
     const int P = t.size, me = t.my_idx, mw = s.my_pe;
-    const int sl = (int)(g.seq++ % 2);
     const bool tr = g_strace.on();
     double tp = tr ? now_s() : 0;
     auto phase = [&](int ph) {
@@ -481,8 +521,7 @@ void small_path_reduce(int alg, void *target, const void *source, size_t count, 
         }
     };
     // 1. my slot is free once every receiver of its previous post has read it
-    for (const auto &u : g.slot_users[sl]) wait_ge(ctl(u.first)->consumed[mw].v, u.second, "a peer to read a slot");
-    g.slot_users[sl].clear();
+    const int sl = claim_slot();
     phase(0);
     const bool bcast = sosplan::is_bcast(alg);
     const int root = bcast ? (alg - sosplan::PLAN_BCAST) / 2 : -1;
@@ -494,29 +533,7 @@ void small_path_reduce(int alg, void *target, const void *source, size_t count, 
     const bool staged = dev_src && (!bcast || me == root);
     if ((!bcast || me == root) && !staged) memcpy(g.host + slot_off(mw, sl), source, bytes);
     // 2. publish it to the team, then take the peers' posts
-    std::atomic_thread_fence(std::memory_order_release);
-    SmallCtl *mine = ctl(mw);
-    uint64_t *words[kMaxPE];
-    uint64_t vals[kMaxPE];
-    int nw = 0;
-    for (int i = 0; i < P; ++i) {
-        if (i == me) continue;
-        const int r = t.world_rank(i);
-        const uint64_t k = ++g.posted_to[r];
-        mine->ring[r][k % 2] = (uint32_t)sl;
-        if (staged) {  // the copy kernel's post: the device view of the same word
-            words[nw] = (uint64_t *)(g.dev + ((char *)&mine->posted[r].v - g.host));
-            vals[nw++] = k;
-        } else {
-            mine->posted[r].v.store(k, std::memory_order_release);
-        }
-        g.slot_users[sl].push_back({r, k});
-    }
-    if (staged) {
-        std::atomic_thread_fence(std::memory_order_seq_cst);  // the slot ids before the launch
-        const int rc = sosx_small_stage(g.dev + slot_off(mw, sl), source, bytes, words, vals, nw, s.stream);
-        if (rc) raise_error("%s: small-path copy of a device operand failed (status %d)", fn, rc);
-    }
+    post_slot(t, sl, staged, 0, source, bytes, fn);
     phase(1);
     const void *in[kMaxPE];
     int from[kMaxPE];
@@ -592,8 +609,7 @@ void small_path_reduce(int alg, void *target, const void *source, size_t count, 
     //    peers' slots are read: acknowledge; my result out
     wait_flags(g.flags, nblocks, g.fseq, fn);
     phase(4);
-    for (int i = 0; i < P; ++i)
-        if (from[i] >= 0) mine->consumed[from[i]].v.store(g.seen_from[from[i]], std::memory_order_release);
+    ack_slots(from, P);
     if (!direct && out) memcpy(target, g.out, bytes);
     g.calls++;
     if (dev_src || dev_dst) g.dev_calls++;
@@ -646,9 +662,7 @@ bool small_collect_exchange(const Team &t, const void *source, size_t bytes, uin
     if (!g.ready || !g.collect_on || t.size < 2 || t.size > kMaxPE || t.my_idx < 0) return false;
     State &s = st();
     const int P = t.size, me = t.my_idx, mw = s.my_pe;
-    const int sl = (int)(g.seq++ % 2);
-    for (const auto &u : g.slot_users[sl]) wait_ge(ctl(u.first)->consumed[mw].v, u.second, "a peer to read a slot");
-    g.slot_users[sl].clear();
+    const int sl = claim_slot();
     const bool dev_src = bytes && is_device_ptr(source);
     const bool has = bytes <= collect_cap(P, dev_src) && (!dev_src || is_local_device_ptr(source));
     const bool staged = has && dev_src;
@@ -656,30 +670,7 @@ bool small_collect_exchange(const Team &t, const void *source, size_t bytes, uin
     const uint64_t hdr[2] = {bytes, has ? 1u : 0u};
     memcpy(slot, hdr, sizeof(hdr));
     if (has && bytes && !staged) memcpy(slot + kCollectHeader, source, bytes);
-    std::atomic_thread_fence(std::memory_order_release);
-    SmallCtl *mine = ctl(mw);
-    uint64_t *words[kMaxPE];
-    uint64_t vals[kMaxPE];
-    int nw = 0;
-    for (int i = 0; i < P; ++i) {
-        if (i == me) continue;
-        const int r = t.world_rank(i);
-        const uint64_t k = ++g.posted_to[r];
-        mine->ring[r][k % 2] = (uint32_t)sl;
-        if (staged) {
-            words[nw] = (uint64_t *)(g.dev + ((char *)&mine->posted[r].v - g.host));
-            vals[nw++] = k;
-        } else {
-            mine->posted[r].v.store(k, std::memory_order_release);
-        }
-        g.slot_users[sl].push_back({r, k});
-    }
-    if (staged) {
-        std::atomic_thread_fence(std::memory_order_seq_cst);  // header and slot ids before the launch
-        const int rc = sosx_small_stage(g.dev + slot_off(mw, sl) + kCollectHeader, source, bytes, words,
-                                        vals, nw, s.stream);
-        if (rc) raise_error("%s: small-path copy of a device operand failed (status %d)", fn, rc);
-    }
+    post_slot(t, sl, staged, kCollectHeader, source, bytes, fn);  // the header is the host's
     g.cx_staged = staged;
     bool all = has;
     for (int i = 0; i < P; ++i) {
@@ -710,7 +701,6 @@ void small_collect_finish(const Team &t, void *target, const uint64_t *lens, boo
 {
     State &s = st();
     const int P = t.size;
-    SmallCtl *mine = ctl(s.my_pe);
     if (take) {
         size_t n[kMaxPE], sum = 0;
         for (int i = 0; i < P; ++i) sum += n[i] = (size_t)lens[i];
@@ -733,9 +723,7 @@ void small_collect_finish(const Team &t, void *target, const uint64_t *lens, boo
         }
         g.collect_calls++;
     }
-    for (int i = 0; i < P; ++i)
-        if (g.cx_from[i] >= 0)
-            mine->consumed[g.cx_from[i]].v.store(g.seen_from[g.cx_from[i]], std::memory_order_release);
+    ack_slots(g.cx_from, P);
 }
 
 // ---------------------------------------------------------------------------------

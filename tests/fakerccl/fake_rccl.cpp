@@ -5,7 +5,7 @@
 // ncclRecv, ncclAllGather, ncclAllReduce), linked with hidden visibility into a test copy of the library,
 // tests/fakerccl/libsos_amd_fakerccl.so.  Real RCCL refuses two ranks on one GPU
 // ("Duplicate GPU detected"), and the GPU box has one, so without this the RCCL executor
-// (collectives.cpp exec_rccl, the RCCL device barrier and team words in runtime.cpp) only
+// (executor.cpp exec_rccl, the RCCL device barrier and team words in runtime.cpp) only
 // ever runs with several PEs on the driver's 8-GPU node.  With it, the same executor code
 // runs with P real PE processes on one GPU, and every plan's send/receive pairing, byte
 // offsets and stream ordering are checked bit-exactly by the same checkers as the p2p runs.

@@ -1,6 +1,6 @@
 """CPU: the stripe decomposition of host-resident ring reductions is bit-exact.
 
-striped_host_ring (sos_amd/csrc/collectives.cpp) runs SOS's ring over "stripes": stripe k
+striped_host_ring (sos_amd/csrc/executor.cpp) runs SOS's ring over "stripes": stripe k
 takes the k-th slice [k*L, k*L + L_k) of EVERY ring chunk (src/collectives.c:697-709),
 and the n mod P extra elements of chunks c < r form a last stripe of r elements.  Each
 stripe runs as an ordinary ring over its own elements.  Here the oracle checks the claim
