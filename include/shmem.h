@@ -149,4 +149,7 @@ int pshmem_broadcastmem(shmem_team_t team, void *dest, const void *source, size_
 /* ---- collect: per-PE lengths (generated: gen_bindings.py) ------------------- */
 #include "shmem_collectv.h"
 
+/* ---- one-sided put / get / p / g / iput / iget, shmem_ptr (generated) ------- */
+#include "shmem_rma.h"
+
 #endif /* SHMEM_H */

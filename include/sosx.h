@@ -214,6 +214,21 @@ int sosx_gather(int nseg, const void *const *srcs, void *const *dsts, const size
 int sosx_strided_copy(void *dst, ptrdiff_t dst_stride, const void *src, ptrdiff_t src_stride,
                       size_t elem_size, size_t count, void *stream);
 
+/* Block-strided copy on device memory (either side may be a mapped peer heap), async on
+ * `stream`: block i of bsize elements goes from src + i * src_stride to
+ * dst + i * dst_stride, i < nblocks; strides in elements and >= bsize, elem_size 1, 2, 4,
+ * 8 or 16, pointers multiples of elem_size.  The data movement of shmemx_ibput / ibget
+ * (shmem_iput / iget: bsize 1).  Bytes between target blocks are never written.
+ * Arguments are checked before any device work (SOSX_ERR_ARG); bsize or nblocks 0 is a
+ * no-op. */
+int sosx_block_strided_copy(void *dst, ptrdiff_t dst_stride, const void *src, ptrdiff_t src_stride,
+                            size_t bsize, size_t nblocks, size_t elem_size, void *stream);
+/* The split that call would use (sos_amd/csrc/blockcopy_plan.h): out = regime, access
+ * width, unaligned loads, head bytes, body accesses per block, tail bytes, body
+ * workgroups, edge workgroups. */
+int sosx_block_copy_plan(uintptr_t dst, ptrdiff_t dst_stride, uintptr_t src, ptrdiff_t src_stride,
+                         size_t bsize, size_t nblocks, size_t elem_size, long long out[8]);
+
 /* p2p transport signalling (internal): store wval[i] to waddr[i] (i < nw) in stream
  * order, then wait until *qaddr[i] >= qval[i] (i < nq); a wait longer than limit_ticks
  * of the device wall clock sets *err and gives up.  Addresses are device views of

@@ -238,6 +238,17 @@ def strided_copy(dst_ptr, dst_stride, src_ptr, src_stride, elem_size, count, str
                                          stream), "sosx_strided_copy")
 
 
+def block_strided_copy(dst_ptr, dst_stride, src_ptr, src_stride, bsize, nblocks, elem_size, stream=None):
+    """Block i of bsize elements from src + i * src_stride to dst + i * dst_stride, i < nblocks, on
+    device memory (sosx_block_strided_copy; strides in elements)."""
+    f = lib().sosx_block_strided_copy
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_void_p, ctypes.c_ssize_t, ctypes.c_void_p, ctypes.c_ssize_t, ctypes.c_size_t,
+                  ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+    return check(f(dst_ptr, dst_stride, src_ptr, src_stride, bsize, nblocks, elem_size, stream),
+                 "sosx_block_strided_copy")
+
+
 def plan_extents(alg, P, count, ts):
     """(src_bytes, dst_bytes) of plan `alg` over P PEs (sosx_plan_extents)."""
     a = ALGS[alg] if isinstance(alg, str) else int(alg)

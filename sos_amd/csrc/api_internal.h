@@ -2,6 +2,7 @@
 // broadcasts and scans (reductions_gen.cpp).
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
 
 #include "shmem.h"
 
@@ -39,6 +40,68 @@ int sos_api_alltoall(shmem_team_t team, void *dest, const void *source, size_t n
                      size_t type_size, const char *fn);
 int sos_api_alltoalls(shmem_team_t team, void *dest, const void *source, ptrdiff_t dst,
                       ptrdiff_t sst, size_t nelems, size_t type_size, const char *fn);
+
+// ---- one-sided put / get (rma.cpp) -------------------------------------------------------
+// SHMEM_DEF_PUT / _PUT_NBI / _GET / _GET_NBI and their sized and mem forms
+// (src/data_c.c4:327-473); nbi: only enqueued on the library stream
+void sos_api_put(void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi,
+                 const char *fn);
+void sos_api_get(void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi,
+                 const char *fn);
+// SHMEM_DEF_IPUT / _IGET (src/data_c.c4:475-497, :560-640): strides in elements
+void sos_api_iput(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                  size_t type_size, int pe, const char *fn);
+void sos_api_iget(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                  size_t type_size, int pe, const char *fn);
+// SHMEM_DEF_IBPUT / _IBGET (src/data_c.c4:499-524): nblocks blocks of bsize elements
+void sos_api_ibput(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize,
+                   size_t nblocks, size_t type_size, int pe, const char *fn);
+void sos_api_ibget(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize,
+                   size_t nblocks, size_t type_size, int pe, const char *fn);
+// SHMEM_DEF_P / SHMEM_DEF_G (src/data_c.c4:300-325): a put / get of one element
+void sos_api_p(void *addr, const void *value, size_t type_size, int pe, const char *fn);
+void sos_api_g(void *value, const void *addr, size_t type_size, int pe, const char *fn);
+// shmem_ptr: the address itself for the calling PE, the mapped address of a device-heap
+// address on a mapped peer, NULL otherwise (never aborts)
+void *sos_api_ptr(const void *dest, int pe);
+
+// The argument checks of the entries above as one function of plain data, so that every
+// refusal can be exercised without a running job: 0, or a code with its message.
+enum {
+    SOS_RMA_OK = 0,
+    SOS_RMA_NOT_INITIALIZED = 1,
+    SOS_RMA_BAD_PE = 2,
+    SOS_RMA_NOT_POSITIVE = 3,    // iput / iget stride <= 0 (SHMEM_ERR_CHECK_POSITIVE)
+    SOS_RMA_NOT_SYMMETRIC = 4,   // remote side outside every symmetric region, or past its end
+    SOS_RMA_NULL_LOCAL = 5,
+    SOS_RMA_STRIDE_LT_BSIZE = 6,
+    SOS_RMA_OVERLAP = 7,         // pe == my_pe and the two extents intersect
+    SOS_RMA_PEER_NOT_DEVICE_HEAP = 8,  // another PE's host heap, data segment or plain allocation
+    SOS_RMA_NO_PATH = 9,         // another PE whose device heap is not mapped here
+    SOS_RMA_BAD_TYPE_SIZE = 10,
+};
+enum { SOS_RMA_REGION_HOST_HEAP = 0, SOS_RMA_REGION_DEVICE_HEAP = 1, SOS_RMA_REGION_DATA = 2,
+       SOS_RMA_REGION_DEVICE_ALLOC = 3 };
+typedef struct {
+    uintptr_t base;
+    size_t size;
+    int kind;
+} sos_rma_region;
+typedef struct {
+    int initialized, my_pe, n_pes;
+    int mapped;  // every peer's device heap is mapped on this PE
+    int nregions;
+    const sos_rma_region *regions;
+} sos_rma_layout;
+typedef struct {
+    const void *remote, *local;
+    ptrdiff_t remote_stride, local_stride;  // elements
+    size_t bsize, nblocks, type_size;
+    int pe;
+    int put;      // the remote side is the target
+    int strided;  // iput / iget: the strides must be positive
+} sos_rma_op;
+int sos_rma_check(const sos_rma_layout *layout, const sos_rma_op *op, char *msg, size_t msg_len);
 
 #ifdef __cplusplus
 }

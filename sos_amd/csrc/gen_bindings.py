@@ -26,6 +26,16 @@ makes their min/max compare signed -- and writes:
                                   active-set shmem_collect32/64, generics and overloads
   sos_amd/csrc/collectv_gen.cpp   their definitions (src/collectives_c.c4:432-503)
 
+  include/shmem_rma.h             the one-sided family: shmem_<T>_{put,get,put_nbi,get_nbi,p,g,
+                                  iput,iget}, the sized and mem forms, shmem_ptr, generics and
+                                  overloads (mpp/shmem_c_func.h4:46-241)
+  include/shmemx_rma.h            shmemx_<T>_{ibput,ibget} and shmemx_{ibput,ibget}<N>
+                                  (mpp/shmemx_c_func.h4:32-71)
+  sos_amd/csrc/rma_gen.cpp        their definitions (src/data_c.c4:300-680) over rma.cpp
+
+The library's Makefile compiles every *.cpp of the directory, so a new generated source
+needs no entry there.
+
 Run: python sos_amd/csrc/gen_bindings.py  (build() runs it; output is committed).
 """
 import os
@@ -373,6 +383,166 @@ def family_source(fam):
     return "\n".join(out)
 
 
+# ---- one-sided put / get (SHMEM_DECLARE_FOR_RMA over the RMA table, SHMEM_DECLARE_FOR_SIZES
+# over 8..128: mpp/shmem_c_func.h4:46-241, mpp/shmemx_c_func.h4:32-71, src/data_c.c4:300-680)
+RMA_SIZES = (8, 16, 32, 64, 128)
+_RMA_CONTIG = ("put", "get", "put_nbi", "get_nbi")
+_RMA_STRIDED = ("iput", "iget")
+_RMA_BLOCK = ("ibput", "ibget")
+_STRIDED_ARGS = "ptrdiff_t tst, ptrdiff_t sst, size_t len, int pe"
+_BLOCK_ARGS = "ptrdiff_t tst, ptrdiff_t sst, size_t bsize, size_t nblocks, int pe"
+
+
+def _rma_call(kind, size, name):
+    """The generic entry behind one form; `size` is a C expression for the element size."""
+    if kind in _RMA_CONTIG:
+        api, nbi = kind.split("_")[0], 1 if kind.endswith("_nbi") else 0
+        return f'sos_api_{api}(target, source, nelems, {size}, pe, {nbi}, "{name}");'
+    if kind in _RMA_STRIDED:
+        return f'sos_api_{kind}(target, source, tst, sst, len, {size}, pe, "{name}");'
+    return f'sos_api_{kind}(target, source, tst, sst, bsize, nblocks, {size}, pe, "{name}");'
+
+
+def rma_entries():
+    """(header, name, sig(prefix), body) of every generated one-sided entry; header is
+    'shmem' or 'shmemx'."""
+    out = []
+
+    def add(hdr, name, proto, body):
+        # proto has one "{p}" where the pshmem prefix goes
+        out.append((hdr, name, lambda p, proto=proto: proto.format(p=p), body))
+
+    for st, ct in RMA:
+        for kind in _RMA_CONTIG:
+            name = f"shmem_{st}_{kind}"
+            add("shmem", name, f"void {{p}}{name}({ct} *target, const {ct} *source, size_t nelems, int pe)",
+                _rma_call(kind, f"sizeof({ct})", name))
+        name = f"shmem_{st}_p"
+        add("shmem", name, f"void {{p}}{name}({ct} *addr, {ct} value, int pe)",
+            f'sos_api_p(addr, &value, sizeof({ct}), pe, "{name}");')
+        name = f"shmem_{st}_g"
+        add("shmem", name, f"{ct} {{p}}{name}(const {ct} *addr, int pe)",
+            f'{ct} tmp; sos_api_g(&tmp, addr, sizeof({ct}), pe, "{name}"); return tmp;')
+        for kind in _RMA_STRIDED:
+            name = f"shmem_{st}_{kind}"
+            add("shmem", name, f"void {{p}}{name}({ct} *target, const {ct} *source, {_STRIDED_ARGS})",
+                _rma_call(kind, f"sizeof({ct})", name))
+        for kind in _RMA_BLOCK:
+            name = f"shmemx_{st}_{kind}"
+            add("shmemx", name, f"void {{p}}{name}({ct} *target, const {ct} *source, {_BLOCK_ARGS})",
+                _rma_call(kind, f"sizeof({ct})", name))
+    for bits in RMA_SIZES:
+        for kind in _RMA_CONTIG:
+            base, _, nbi = kind.partition("_")
+            name = f"shmem_{base}{bits}" + ("_nbi" if nbi else "")
+            add("shmem", name, f"void {{p}}{name}(void *target, const void *source, size_t nelems, int pe)",
+                _rma_call(kind, str(bits // 8), name))
+        for kind in _RMA_STRIDED:
+            name = f"shmem_{kind}{bits}"
+            add("shmem", name, f"void {{p}}{name}(void *target, const void *source, {_STRIDED_ARGS})",
+                _rma_call(kind, str(bits // 8), name))
+        for kind in _RMA_BLOCK:
+            name = f"shmemx_{kind}{bits}"
+            add("shmemx", name, f"void {{p}}{name}(void *target, const void *source, {_BLOCK_ARGS})",
+                _rma_call(kind, str(bits // 8), name))
+    for kind in _RMA_CONTIG:
+        base, _, nbi = kind.partition("_")
+        name = f"shmem_{base}mem" + ("_nbi" if nbi else "")
+        add("shmem", name, f"void {{p}}{name}(void *target, const void *source, size_t nelems, int pe)",
+            _rma_call(kind, "1", name))
+    return out
+
+
+def rma_symbols():
+    """Every public one-sided name, shmem_ptr (written by hand in rma.cpp) included."""
+    return [name for _, name, _, _ in rma_entries()] + ["shmem_ptr"]
+
+
+def _rma_generic_args(kind):
+    """(C++ parameter list after the two pointers, call arguments) of one generic."""
+    if kind in _RMA_CONTIG:
+        return "size_t nelems, int pe", "nelems, pe"
+    if kind in _RMA_STRIDED:
+        return _STRIDED_ARGS, "tst, sst, len, pe"
+    return _BLOCK_ARGS, "tst, sst, bsize, nblocks, pe"
+
+
+def _rma_generics(prefix, kinds, with_pg):
+    """The C++ overloads and the C11 selectors of `kinds` (and shmem_p / shmem_g)."""
+    out = ["#if defined(__cplusplus)"]
+    for kind in kinds:
+        params, args = _rma_generic_args(kind)
+        for st, ct in GENERIC_RMA:
+            out.append(f"static inline void {prefix}_{kind}({ct} *target, const {ct} *source, {params}) "
+                       f"{{ {prefix}_{st}_{kind}(target, source, {args}); }}")
+    if with_pg:
+        for st, ct in GENERIC_RMA:
+            out.append(f"static inline void shmem_p({ct} *addr, {ct} value, int pe) "
+                       f"{{ shmem_{st}_p(addr, value, pe); }}")
+        for st, ct in GENERIC_RMA:
+            out.append(f"static inline {ct} shmem_g(const {ct} *addr, int pe) {{ return shmem_{st}_g(addr, pe); }}")
+    out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
+    out += c11_prelude()
+    # there is no context argument here: the selector looks at the first argument
+    out += ["#ifndef SHMEM_C11_ARG0", "#define SHMEM_C11_ARG0(...) SHMEM_C11_ARG0_HELPER(__VA_ARGS__, sentinel)",
+            "#define SHMEM_C11_ARG0_HELPER(first, ...) first", "#endif"]
+    for kind in kinds:
+        out += c11_generic(f"{prefix}_{kind}", [f"        {ct}*: {prefix}_{st}_{kind}" for st, ct in GENERIC_RMA],
+                           argidx=0)
+    if with_pg:
+        out += c11_generic("shmem_p", [f"        {ct}*: shmem_{st}_p" for st, ct in GENERIC_RMA], argidx=0)
+        out += c11_generic("shmem_g", [f"        {ct}*: shmem_{st}_g, \\\n        const {ct}*: shmem_{st}_g"
+                                       for st, ct in GENERIC_RMA], argidx=0)
+    out.append("#endif")
+    return out
+
+
+def rma_header(which):
+    fname = "shmem_rma.h" if which == "shmem" else "shmemx_rma.h"
+    guard = fname.upper().replace(".", "_")
+    out = [f"/* {fname} -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", " *"]
+    if which == "shmem":
+        out += [" * SOS's one-sided put / get family on the symmetric heaps: the typed forms",
+                " * shmem_<T>_{put,get,put_nbi,get_nbi,p,g,iput,iget} over the 24 RMA types, the sized",
+                " * forms for 8..128 bits, putmem / getmem, shmem_ptr, the C11 generic selectors and the",
+                " * C++ overloads (mpp/shmem_c_func.h4:46-241).  There are no contexts: the shmem_ctx_*",
+                " * forms are not provided.  Included from shmem.h. */"]
+    else:
+        out += [" * SOS's block-strided extension shmemx_<T>_{ibput,ibget} and shmemx_{ibput,ibget}<N>",
+                " * (mpp/shmemx_c_func.h4:32-71): nblocks blocks of bsize elements, tst / sst elements",
+                " * apart.  Included from shmemx.h. */"]
+    out += [f"#ifndef {guard}", f"#define {guard}", "", "#ifdef __cplusplus", 'extern "C" {', "#endif", ""]
+    entries = [e for e in rma_entries() if e[0] == which]
+    for _, name, sig, _ in entries:
+        out.append(f"SHMEM_FUNCTION_ATTRIBUTES {sig('')};")
+    if which == "shmem":
+        out.append("SHMEM_FUNCTION_ATTRIBUTES void *shmem_ptr(const void *target, int pe);")
+    out += ["", "/* profiling interface: pshmem_* are the implementations, shmem_* weak aliases */"]
+    for _, name, sig, _ in entries:
+        out.append(f"{sig('p')};")
+    if which == "shmem":
+        out.append("void *pshmem_ptr(const void *target, int pe);")
+    out += ["", "#ifdef __cplusplus", "}  /* extern \"C\" */", "#endif", ""]
+    if which == "shmem":
+        out += _rma_generics("shmem", _RMA_CONTIG + _RMA_STRIDED, True)
+    else:
+        out += _rma_generics("shmemx", _RMA_BLOCK, False)
+    out += ["", f"#endif /* {guard} */", ""]
+    return "\n".join(out)
+
+
+def rma_source():
+    out = ["// rma_gen.cpp -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", "//",
+           "// The typed, sized and mem forms of put / get / p / g / iput / iget and of SOS's",
+           "// shmemx ibput / ibget (SHMEM_DEF_PUT ... SHMEM_DEF_IBGET_N over SHMEM_BIND_C_RMA and",
+           "// SHMEM_BIND_C_SIZES, src/data_c.c4:300-680): strong pshmem_*, weak shmem_* aliases.",
+           '#include "shmem.h"', '#include "shmemx.h"', '#include "api_internal.h"', "", 'extern "C" {', ""]
+    for _, name, sig, body in rma_entries():
+        definition(out, sig, name, body)
+    out += ['}  // extern "C"', ""]
+    return "\n".join(out)
+
+
 def collect_symbols():
     """The generated fcollect / alltoall / alltoalls names (typed forms only)."""
     return [f"shmem_{st}_{kind}" for kind in COLLECTS for st, ct in RMA]
@@ -401,6 +571,10 @@ def main():
     for fam in FAMILIES.values():
         targets[os.path.join(ROOT, "include", fam["header"])] = family_header(fam)
         targets[os.path.join(ROOT, "sos_amd", "csrc", fam["source"])] = family_source(fam)
+    assert len(rma_symbols()) == 24 * 10 + 5 * 8 + 4 + 1, len(rma_symbols())
+    targets[os.path.join(ROOT, "include", "shmem_rma.h")] = rma_header("shmem")
+    targets[os.path.join(ROOT, "include", "shmemx_rma.h")] = rma_header("shmemx")
+    targets[os.path.join(ROOT, "sos_amd", "csrc", "rma_gen.cpp")] = rma_source()
     check = "--check" in sys.argv
     stale = False
     for path, text in targets.items():

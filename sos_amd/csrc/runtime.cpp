@@ -662,6 +662,23 @@ void team_barrier(const Team &t)
     hip_check(sync_system(s.stream), "hipStreamSynchronize(barrier)");
 }
 
+// A barrier or sync the program called.  team_barrier completes the stream with a
+// system-scope release before it signals (the producer half: what this PE put is in the
+// peers' HBM when they leave the barrier).  The consumer half: a peer may have put into
+// this PE's heap before the barrier (rma.cpp), so the barrier counts as a wait for a
+// peer's bytes, and the acquire follows it at once in stream order -- every later launch
+// of the library or the program on this stream reads local symmetric memory behind it.
+// Only where peers can store here at all: the heaps are mapped (p2p transport).
+void user_barrier(const Team &t)
+{
+    team_barrier(t);
+    State &s = st();
+    if (t.size > 1 && t.my_idx >= 0 && s.n_pes > 1 && s.p2p_ready) {
+        note_peer_wait();
+        hip_check(acquire_system(s.stream), "acquire after barrier");
+    }
+}
+
 Team *team_from_handle(shmem_team_t handle) { return reinterpret_cast<Team *>(handle); }
 
 // ---------------------------------------------------------------------------------
@@ -1187,7 +1204,7 @@ int shmemx_set_reduce_algorithm(int alg)
 void shmem_barrier_all(void)
 {
     check_initialized("shmem_barrier_all");
-    team_barrier(st().world);
+    user_barrier(st().world);
 }
 
 void shmem_sync_all(void) { shmem_barrier_all(); }
@@ -1225,7 +1242,7 @@ void shmem_sync(int PE_start, int logPE_stride, int PE_size, long *pSync)
 {
     check_initialized("shmem_sync");
     (void)pSync;
-    team_barrier(active_set(PE_start, logPE_stride, PE_size, "shmem_sync"));
+    user_barrier(active_set(PE_start, logPE_stride, PE_size, "shmem_sync"));
 }
 
 void shmem_barrier(int PE_start, int logPE_stride, int PE_size, long *pSync)
@@ -1493,7 +1510,7 @@ void shmem_team_destroy(shmem_team_t team)
 int shmem_team_sync(shmem_team_t team)
 {
     if (team == SHMEM_TEAM_INVALID) return -1;
-    team_barrier(*team_checked(team, "shmem_team_sync"));
+    user_barrier(*team_checked(team, "shmem_team_sync"));
     return 0;
 }
 

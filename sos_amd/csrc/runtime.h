@@ -196,6 +196,9 @@ bool is_symmetric(const void *p, size_t bytes);
 
 // Barrier across a team: dissemination over RCCL point-to-point, host-synchronous.
 void team_barrier(const Team &t);
+// The barriers and syncs of the public API: team_barrier, then the consumer-side acquire
+// for what peers may have put into this PE's heap before it (p2p transport only).
+void user_barrier(const Team &t);
 
 // shmem_team_t is SOS's opaque `struct shmem_impl_team_t *` (mpp/shmem-def.h.in:94-96);
 // the object behind it is a Team.

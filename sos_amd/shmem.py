@@ -81,6 +81,27 @@ _RUNTIME = {
                                  _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
     "shmem_alltoalls64": (None, [_c.c_void_p, _c.c_void_p, _c.c_ssize_t, _c.c_ssize_t, _c.c_size_t,
                                  _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    # one-sided put / get: the generic entries behind the typed forms (rma.cpp), for the tests
+    "shmem_quiet": (None, []),
+    "shmem_fence": (None, []),
+    "sos_api_put": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_int, _c.c_int, _c.c_char_p]),
+    "sos_api_get": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_int, _c.c_int, _c.c_char_p]),
+    "sos_api_iput": (None, [_c.c_void_p, _c.c_void_p, _c.c_ssize_t, _c.c_ssize_t, _c.c_size_t, _c.c_size_t,
+                            _c.c_int, _c.c_char_p]),
+    "sos_api_iget": (None, [_c.c_void_p, _c.c_void_p, _c.c_ssize_t, _c.c_ssize_t, _c.c_size_t, _c.c_size_t,
+                            _c.c_int, _c.c_char_p]),
+    "sos_api_ibput": (None, [_c.c_void_p, _c.c_void_p, _c.c_ssize_t, _c.c_ssize_t, _c.c_size_t, _c.c_size_t,
+                             _c.c_size_t, _c.c_int, _c.c_char_p]),
+    "sos_api_ibget": (None, [_c.c_void_p, _c.c_void_p, _c.c_ssize_t, _c.c_ssize_t, _c.c_size_t, _c.c_size_t,
+                             _c.c_size_t, _c.c_int, _c.c_char_p]),
+    "sos_api_p": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_char_p]),
+    "sos_api_g": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_char_p]),
+    "sos_api_ptr": (_c.c_void_p, [_c.c_void_p, _c.c_int]),
+    "shmem_ptr": (_c.c_void_p, [_c.c_void_p, _c.c_int]),
+    "sosx_block_strided_copy": (_c.c_int, [_c.c_void_p, _c.c_ssize_t, _c.c_void_p, _c.c_ssize_t, _c.c_size_t,
+                                           _c.c_size_t, _c.c_size_t, _c.c_void_p]),
+    "sosx_block_copy_plan": (_c.c_int, [_c.c_void_p, _c.c_ssize_t, _c.c_void_p, _c.c_ssize_t, _c.c_size_t,
+                                        _c.c_size_t, _c.c_size_t, _c.POINTER(_c.c_longlong)]),
     "sosx_prof_enable": (None, [_c.c_int]),
     "sosx_prof_get": (None, [_c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                              _c.POINTER(_c.c_long), _c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
@@ -90,6 +111,15 @@ _REDUCE_RE = re.compile(r"^shmem_(\w+?)_(and|or|xor|min|max|sum|prod)_(reduce|to
 _SCAN_RE = re.compile(r"^shmemx_(\w+?)_sum_(inscan|exscan)$")
 _BCAST_RE = re.compile(r"^shmem_(\w+?)_broadcast$")
 _COLLECT_RE = re.compile(r"^shmem_(\w+?)_(fcollect|alltoalls|alltoall|collect)$")
+# shmem_<T>_put / get / put_nbi / get_nbi / iput / iget / p / g, shmem_put<N> ..., putmem / getmem,
+# shmemx_<T>_ibput / ibget and shmemx_ibput<N> / ibget<N>
+_RMA_RE = re.compile(r"^shmemx?_(?:(\w+?)_)?(ibput|ibget|iput|iget|put|get|p|g)(\d+|mem)?(_nbi)?$")
+_BY_VALUE = {"char": _c.c_char, "schar": _c.c_byte, "short": _c.c_short, "int": _c.c_int, "long": _c.c_long,
+             "longlong": _c.c_longlong, "uchar": _c.c_ubyte, "ushort": _c.c_ushort, "uint": _c.c_uint,
+             "ulong": _c.c_ulong, "ulonglong": _c.c_ulonglong, "int8": _c.c_int8, "int16": _c.c_int16,
+             "int32": _c.c_int32, "int64": _c.c_int64, "uint8": _c.c_uint8, "uint16": _c.c_uint16,
+             "uint32": _c.c_uint32, "uint64": _c.c_uint64, "size": _c.c_size_t, "ptrdiff": _c.c_ssize_t,
+             "float": _c.c_float, "double": _c.c_double, "longdouble": _c.c_longdouble}
 _declared = False
 
 
@@ -152,6 +182,24 @@ def __getattr__(name):
         return fn
     if name in _RUNTIME:
         return getattr(L, name)
+    m = _RMA_RE.match(name)
+    if m and (m.group(1) is None or m.group(1) in _BY_VALUE):
+        ty, kind = m.group(1), m.group(2)
+        fn = getattr(L, name)
+        fn.restype = None
+        if kind == "p":
+            fn.argtypes = [_c.c_void_p, _BY_VALUE[ty], _c.c_int]
+        elif kind == "g":
+            fn.restype = _BY_VALUE[ty]
+            fn.argtypes = [_c.c_void_p, _c.c_int]
+        elif kind in ("put", "get"):
+            fn.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int]
+        elif kind in ("iput", "iget"):
+            fn.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_ssize_t, _c.c_ssize_t, _c.c_size_t, _c.c_int]
+        else:
+            fn.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_ssize_t, _c.c_ssize_t, _c.c_size_t, _c.c_size_t,
+                           _c.c_int]
+        return fn
     raise AttributeError(name)
 
 
