@@ -152,4 +152,7 @@ int pshmem_broadcastmem(shmem_team_t team, void *dest, const void *source, size_
 /* ---- one-sided put / get / p / g / iput / iget, shmem_ptr (generated) ------- */
 #include "shmem_rma.h"
 
+/* ---- atomic memory operations shmem_<T>_atomic_* (generated) ---------------- */
+#include "shmem_amo.h"
+
 #endif /* SHMEM_H */

@@ -229,6 +229,27 @@ int sosx_block_strided_copy(void *dst, ptrdiff_t dst_stride, const void *src, pt
 int sosx_block_copy_plan(uintptr_t dst, ptrdiff_t dst_stride, uintptr_t src, ptrdiff_t src_stride,
                          size_t bsize, size_t nblocks, size_t elem_size, long long out[8]);
 
+/* ---- atomic memory operations (shmem_<T>_atomic_*) --------------------------- */
+#define SOSX_AMO_SET   0  /* exchange, old value dropped */
+#define SOSX_AMO_FETCH 1  /* atomic load */
+#define SOSX_AMO_SWAP  2
+#define SOSX_AMO_CSWAP 3  /* value is stored if the word equals cond */
+#define SOSX_AMO_ADD   4  /* inc is ADD 1 */
+#define SOSX_AMO_AND   5
+#define SOSX_AMO_OR    6
+#define SOSX_AMO_XOR   7
+
+/* One atomic operation on the `width`-byte (4 or 8) word at `target`, async on `stream`:
+ * one launch of one wave whose first lane performs one system-scope read-modify-write (an
+ * atomic load for FETCH).  `value` and `cond` hold the operands in their low `width`
+ * bytes; a float or double (is_float) passes its bit pattern and may only SET, FETCH or
+ * SWAP (SOSX_ERR_OP otherwise).  `fetch` (or NULL; required for FETCH) receives the old
+ * value by a plain store, visible to the host or a copy engine after the stream's next
+ * system-scope release.  target and fetch are device-reachable addresses, multiples of
+ * width.  Arguments are checked before any device work (SOSX_ERR_ARG). */
+int sosx_amo(int op, void *target, uint64_t value, uint64_t cond, void *fetch, size_t width,
+             int is_float, void *stream);
+
 /* p2p transport signalling (internal): store wval[i] to waddr[i] (i < nw) in stream
  * order, then wait until *qaddr[i] >= qval[i] (i < nq); a wait longer than limit_ticks
  * of the device wall clock sets *err and gives up.  Addresses are device views of

@@ -7,6 +7,8 @@
 #include "shmem.h"
 
 #ifdef __cplusplus
+#include <vector>
+
 extern "C" {
 #endif
 
@@ -103,6 +105,47 @@ typedef struct {
 } sos_rma_op;
 int sos_rma_check(const sos_rma_layout *layout, const sos_rma_op *op, char *msg, size_t msg_len);
 
+// ---- atomic memory operations (amo.cpp) --------------------------------------------------
+// SHMEM_DEF_SWAP ... SHMEM_DEF_FETCH_XOR and the nbi forms (src/atomic_c.c4:226-560,
+// src/atomic_nbi_c.c4): op is a SOSX_AMO_*; value / cond point at the operands (NULL where
+// the form has none); want_old: the old value goes to *fetch_out -- for the blocking forms
+// the caller's local, filled when the call returns; for the nbi forms the program's
+// `fetch`, filled no later than the next shmem_quiet.
+void sos_api_amo(int op, void *target, const void *value, const void *cond, void *fetch_out, int want_old,
+                 size_t type_size, int is_float, int pe, int nbi, const char *fn);
+// Its checks in SOS's order -- initialized, PE, symmetric over type_size bytes -- then this
+// library's own, over the layout struct of sos_rma_check: 0, or a SOS_RMA_* code (and
+// SOS_AMO_NULL_FETCH) with its message.
+enum { SOS_AMO_NULL_FETCH = 11 };  // an nbi fetching form without a place for the old value
+typedef struct {
+    const void *target;
+    const void *fetch;  // looked at for the nbi forms only
+    size_t type_size;
+    int pe;
+    int nbi;
+} sos_amo_op;
+int sos_amo_check(const sos_rma_layout *layout, const sos_amo_op *op, char *msg, size_t msg_len);
+
 #ifdef __cplusplus
 }
+
+// What rma.cpp and amo.cpp share.
+namespace sosrt {
+struct RmaLayout {
+    std::vector<sos_rma_region> regions;
+    sos_rma_layout l;
+};
+// the symmetric regions and the job's shape as they are now: the checks' input
+void rma_layout_now(RmaLayout &out);
+const sos_rma_region *rma_find_region(const sos_rma_layout *l, uintptr_t p);
+const char *rma_region_name(int kind);
+// the remote side's address on this PE
+char *translate(const void *remote, int pe);
+// Before a launch or copy that reads peer `pe`'s heap: the acquire a wait since the last
+// one left owed, and the read counted.
+void before_peer_read(int pe, const char *fn);
+// The address at which a kernel on this PE's GPU reaches the `bytes` bytes at p, or null
+// where it cannot (rma.cpp).
+char *device_view(const void *p, size_t bytes);
+}  // namespace sosrt
 #endif

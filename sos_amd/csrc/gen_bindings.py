@@ -33,6 +33,11 @@ makes their min/max compare signed -- and writes:
                                   (mpp/shmemx_c_func.h4:32-71)
   sos_amd/csrc/rma_gen.cpp        their definitions (src/data_c.c4:300-680) over rma.cpp
 
+  include/shmem_amo.h             the atomic memory operations shmem_<T>_atomic_*, their
+                                  deprecated names and nbi forms, generics and overloads
+                                  (mpp/shmem_c_func.h4:243-404, :575-639)
+  sos_amd/csrc/amo_gen.cpp        their definitions (src/atomic_c.c4) over amo.cpp
+
 The library's Makefile compiles every *.cpp of the directory, so a new generated source
 needs no entry there.
 
@@ -543,6 +548,149 @@ def rma_source():
     return "\n".join(out)
 
 
+# ---- atomic memory operations (SHMEM_DECLARE_FOR_AMO / _EXTENDED_AMO / _BITWISE_AMO:
+# mpp/shmem_c_func.h4:243-404, :575-639; bindings/shmem_bind_c.m4:43-69; src/atomic_c.c4,
+# src/atomic_nbi_c.c4).  There are no contexts: the shmem_ctx_* forms are not provided.
+AMO = [("int", "int"), ("long", "long"), ("longlong", "long long"), ("uint", "unsigned int"),
+       ("ulong", "unsigned long"), ("ulonglong", "unsigned long long"), ("int32", "int32_t"),
+       ("int64", "int64_t"), ("uint32", "uint32_t"), ("uint64", "uint64_t"), ("size", "size_t"),
+       ("ptrdiff", "ptrdiff_t")]
+EXTENDED_AMO = AMO + [("float", "float"), ("double", "double")]
+BITWISE_AMO = [("uint", "unsigned int"), ("ulong", "unsigned long"), ("ulonglong", "unsigned long long"),
+               ("int32", "int32_t"), ("int64", "int64_t"), ("uint32", "uint32_t"), ("uint64", "uint64_t")]
+AMO_TABLES = {"AMO": AMO, "EXTENDED_AMO": EXTENDED_AMO, "BITWISE_AMO": BITWISE_AMO}
+# the generic selectors' arms (bindings/shmem_bind_c11.m4:30-56, shmem_bind_cxx.m4:30-54)
+_AMO_BASE = AMO[:6]
+AMO_GENERIC_C11 = {"AMO": _AMO_BASE, "EXTENDED_AMO": _AMO_BASE + EXTENDED_AMO[-2:],
+                   "BITWISE_AMO": [("int32", "int32_t"), ("int64", "int64_t")] + BITWISE_AMO[:3]}
+AMO_GENERIC_CXX = {"AMO": _AMO_BASE, "EXTENDED_AMO": _AMO_BASE + EXTENDED_AMO[-2:],
+                   "BITWISE_AMO": BITWISE_AMO[:3]}
+
+# form -> (table, SOSX_AMO_* op, shape, deprecated).  shape: which operands the prototype
+# has -- "v" value, "c" cond, "1" the constant one (inc) -- and whether the old value is
+# returned ("r"), goes to *fetch ("n": the nbi forms) or is dropped ("").
+AMO_FORMS = {}
+for _form, _old, _table, _op, _args in (
+        ("atomic_compare_swap", "cswap", "AMO", "CSWAP", "cv"), ("atomic_fetch_inc", "finc", "AMO", "ADD", "1"),
+        ("atomic_fetch_add", "fadd", "AMO", "ADD", "v"), ("atomic_swap", "swap", "EXTENDED_AMO", "SWAP", "v"),
+        ("atomic_fetch", "fetch", "EXTENDED_AMO", "FETCH", ""), ("atomic_fetch_and", None, "BITWISE_AMO", "AND", "v"),
+        ("atomic_fetch_or", None, "BITWISE_AMO", "OR", "v"), ("atomic_fetch_xor", None, "BITWISE_AMO", "XOR", "v")):
+    AMO_FORMS[_form] = (_table, _op, _args, "r", False)
+    if _old:
+        AMO_FORMS[_old] = (_table, _op, _args, "r", True)
+    AMO_FORMS[_form + "_nbi"] = (_table, _op, _args, "n", False)
+for _form, _old, _table, _op, _args in (
+        ("atomic_inc", "inc", "AMO", "ADD", "1"), ("atomic_add", "add", "AMO", "ADD", "v"),
+        ("atomic_set", "set", "EXTENDED_AMO", "SET", "v"), ("atomic_and", None, "BITWISE_AMO", "AND", "v"),
+        ("atomic_or", None, "BITWISE_AMO", "OR", "v"), ("atomic_xor", None, "BITWISE_AMO", "XOR", "v")):
+    AMO_FORMS[_form] = (_table, _op, _args, "", False)
+    if _old:
+        AMO_FORMS[_old] = (_table, _op, _args, "", True)
+# what a deprecated generic selects in C++ (mpp/shmem.h4:322-387, :452-487: the new name)
+_AMO_RENAMED = {"cswap": "atomic_compare_swap", "finc": "atomic_fetch_inc", "fadd": "atomic_fetch_add",
+                "swap": "atomic_swap", "fetch": "atomic_fetch", "inc": "atomic_inc", "add": "atomic_add",
+                "set": "atomic_set"}
+
+
+def _amo_params(form, ct):
+    """(parameter list, argument names) of one form for C type `ct`."""
+    table, op, args, old, dep = AMO_FORMS[form]
+    params = [f"{ct} *fetch"] if old == "n" else []
+    params.append(f"const {ct} *target" if op == "FETCH" else f"{ct} *target")
+    params += [f"{ct} cond"] if "c" in args else []
+    params += [f"{ct} value"] if "v" in args else []
+    params.append("int pe")
+    return ", ".join(params), ", ".join(p.split()[-1].lstrip("*") for p in params)
+
+
+def _amo_ret(form, ct):
+    return ct if AMO_FORMS[form][3] == "r" else "void"
+
+
+def amo_entries():
+    """(name, sig(prefix), body, deprecated) of every generated atomic entry."""
+    out = []
+    for form, (table, op, args, old, dep) in AMO_FORMS.items():
+        for st, ct in AMO_TABLES[table]:
+            name = f"shmem_{st}_{form}"
+            params, _ = _amo_params(form, ct)
+            proto = f"{_amo_ret(form, ct)} {{p}}{name}({params})"
+            is_float = 1 if st in ("float", "double") else 0
+            pre = f"{ct} value = 1; " if "1" in args else ""
+            value = "&value" if ("v" in args or "1" in args) else "NULL"
+            cond = "&cond" if "c" in args else "NULL"
+            target = "(void *)target" if op == "FETCH" else "target"
+            fetch = {"r": "&old", "n": "fetch", "": "NULL"}[old]
+            call = (f"sos_api_amo(SOSX_AMO_{op}, {target}, {value}, {cond}, {fetch}, {1 if old else 0}, "
+                    f"sizeof({ct}), {is_float}, pe, {1 if old == 'n' else 0}, \"{name}\");")
+            body = pre + (f"{ct} old; {call} return old;" if old == "r" else call)
+            out.append((name, lambda p, proto=proto: proto.format(p=p), body, dep))
+    return out
+
+
+def amo_symbols():
+    """Every public atomic name (typed forms; there are no untyped ones)."""
+    return [name for name, _, _, _ in amo_entries()]
+
+
+def _amo_generics():
+    out = ["#if defined(__cplusplus)"]
+    for form, (table, op, args, old, dep) in AMO_FORMS.items():
+        for st, ct in AMO_GENERIC_CXX[table]:
+            params, names = _amo_params(form, ct)
+            ret = _amo_ret(form, ct)
+            callee = f"shmem_{st}_{_AMO_RENAMED.get(form, form)}"
+            out.append(f"static inline {ret} shmem_{form}({params}) "
+                       f"{{ {'return ' if ret != 'void' else ''}{callee}({names}); }}")
+    out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
+    out += c11_prelude()
+    out += ["#ifndef SHMEM_C11_ARG0", "#define SHMEM_C11_ARG0(...) SHMEM_C11_ARG0_HELPER(__VA_ARGS__, sentinel)",
+            "#define SHMEM_C11_ARG0_HELPER(first, ...) first", "#endif"]
+    for form, (table, op, args, old, dep) in AMO_FORMS.items():
+        arms = [f"        {ct}*: shmem_{st}_{form}" for st, ct in AMO_GENERIC_C11[table]]
+        if op == "FETCH":  # the target is const: both qualifications select (mpp/shmem.h4:1013-1035)
+            arms += [f"        const {ct}*: shmem_{st}_{form}" for st, ct in AMO_GENERIC_C11[table]]
+        out += c11_generic(f"shmem_{form}", arms, argidx=0)
+    out.append("#endif")
+    return out
+
+
+def amo_header():
+    out = ["/* shmem_amo.h -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", " *",
+           " * SOS's atomic memory operations on the symmetric heaps (mpp/shmem_c_func.h4:243-404,",
+           " * :575-639): compare_swap, fetch_inc, inc, fetch_add, add over the 12 AMO types; swap,",
+           " * fetch, set over those and float, double; and, or, xor and their fetching forms over the",
+           " * 7 bitwise types; the deprecated pre-1.4 names; the nbi fetching forms; the C11 generic",
+           " * selectors and the C++ overloads.  There are no contexts: the shmem_ctx_* forms are not",
+           " * provided.  Included from shmem.h. */",
+           "#ifndef SHMEM_AMO_H", "#define SHMEM_AMO_H", "",
+           "#ifndef SHMEM_ATTRIBUTE_DEPRECATED",
+           "#define SHMEM_ATTRIBUTE_DEPRECATED __attribute__((deprecated))", "#endif", "",
+           "#ifdef __cplusplus", 'extern "C" {', "#endif", ""]
+    entries = amo_entries()
+    for name, sig, _, dep in entries:
+        out.append(f"SHMEM_FUNCTION_ATTRIBUTES {sig('')}{' SHMEM_ATTRIBUTE_DEPRECATED' if dep else ''};")
+    out += ["", "/* profiling interface: pshmem_* are the implementations, shmem_* weak aliases */"]
+    for name, sig, _, dep in entries:
+        out.append(f"{sig('p')}{' SHMEM_ATTRIBUTE_DEPRECATED' if dep else ''};")
+    out += ["", "#ifdef __cplusplus", "}  /* extern \"C\" */", "#endif", ""]
+    out += _amo_generics()
+    out += ["", "#endif /* SHMEM_AMO_H */", ""]
+    return "\n".join(out)
+
+
+def amo_source():
+    out = ["// amo_gen.cpp -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", "//",
+           "// The typed atomic memory operations (SHMEM_DEF_SWAP ... SHMEM_DEF_FETCH_XOR over",
+           "// SHMEM_BIND_C_AMO, _EXTENDED_AMO and _BITWISE_AMO, src/atomic_c.c4:226-560, and the nbi",
+           "// forms of src/atomic_nbi_c.c4) over amo.cpp: strong pshmem_*, weak shmem_* aliases.",
+           '#include "shmem.h"', '#include "sosx.h"', '#include "api_internal.h"', "", 'extern "C" {', ""]
+    for name, sig, body, _ in amo_entries():
+        definition(out, sig, name, body)
+    out += ['}  // extern "C"', ""]
+    return "\n".join(out)
+
+
 def collect_symbols():
     """The generated fcollect / alltoall / alltoalls names (typed forms only)."""
     return [f"shmem_{st}_{kind}" for kind in COLLECTS for st, ct in RMA]
@@ -575,6 +723,10 @@ def main():
     targets[os.path.join(ROOT, "include", "shmem_rma.h")] = rma_header("shmem")
     targets[os.path.join(ROOT, "include", "shmemx_rma.h")] = rma_header("shmemx")
     targets[os.path.join(ROOT, "sos_amd", "csrc", "rma_gen.cpp")] = rma_source()
+    n_amo = sum(len(AMO_TABLES[table]) for table, _, _, _, _ in AMO_FORMS.values())
+    assert len(amo_symbols()) == len(set(amo_symbols())) == n_amo, (len(amo_symbols()), n_amo)
+    targets[os.path.join(ROOT, "include", "shmem_amo.h")] = amo_header()
+    targets[os.path.join(ROOT, "sos_amd", "csrc", "amo_gen.cpp")] = amo_source()
     check = "--check" in sys.argv
     stale = False
     for path, text in targets.items():

@@ -37,21 +37,25 @@ using namespace sosrt;
 extern "C" char __data_start[] __attribute__((weak));
 extern "C" char _end[] __attribute__((weak));
 
-namespace {
+namespace sosrt {
 
-const sos_rma_region *find_region(const sos_rma_layout *l, uintptr_t p)
+const sos_rma_region *rma_find_region(const sos_rma_layout *l, uintptr_t p)
 {
     for (int i = 0; i < l->nregions; ++i)
         if (p >= l->regions[i].base && p - l->regions[i].base < l->regions[i].size) return &l->regions[i];
     return nullptr;
 }
 
-const char *region_name(int kind)
+const char *rma_region_name(int kind)
 {
     return kind == SOS_RMA_REGION_HOST_HEAP ? "sym. heap region"
            : kind == SOS_RMA_REGION_DEVICE_HEAP ? "device sym. heap region"
            : kind == SOS_RMA_REGION_DATA ? "sym. data region" : "device allocation";
 }
+
+}  // namespace sosrt
+
+namespace {
 
 // elements spanned by nblocks blocks of bsize at `stride` (>= 0); false if over size_t
 bool extent_bytes(size_t bsize, size_t nblocks, ptrdiff_t stride, size_t ts, size_t *out)
@@ -94,12 +98,12 @@ extern "C" int sos_rma_check(const sos_rma_layout *l, const sos_rma_op *op, char
     if (!empty) {
         // SHMEM_ERR_CHECK_SYMMETRIC over the remote side's whole extent
         const uintptr_t r = (uintptr_t)op->remote;
-        reg = find_region(l, r);
+        reg = rma_find_region(l, r);
         if (!reg) REFUSE(SOS_RMA_NOT_SYMMETRIC, "Argument \"%s\" is not symmetric (%p)", rname, op->remote);
         if (!extent_bytes(op->bsize, op->nblocks, op->remote_stride, ts, &rext) ||
             rext > reg->size - (r - reg->base))
             REFUSE(SOS_RMA_NOT_SYMMETRIC, "Argument \"%s\" [%p..%p) exceeds %s [%p..%p)", rname, op->remote,
-                   (const void *)(r + rext), region_name(reg->kind), (const void *)reg->base,
+                   (const void *)(r + rext), rma_region_name(reg->kind), (const void *)reg->base,
                    (const void *)(reg->base + reg->size));
         // SHMEM_ERR_CHECK_NULL
         if (!op->local) REFUSE(SOS_RMA_NULL_LOCAL, "Argument \"%s\" is NULL", lname);
@@ -132,7 +136,7 @@ extern "C" int sos_rma_check(const sos_rma_layout *l, const sos_rma_op *op, char
     if (reg->kind != SOS_RMA_REGION_DEVICE_HEAP)
         REFUSE(SOS_RMA_PEER_NOT_DEVICE_HEAP, "Argument \"%s\" (%p) is in this PE's %s: put/get to another PE "
                "(%d) needs the device symmetric heap (shmemx_malloc_device), the only memory mapped across PEs",
-               rname, op->remote, region_name(reg->kind), op->pe);
+               rname, op->remote, rma_region_name(reg->kind), op->pe);
     if (!l->mapped)
         REFUSE(SOS_RMA_NO_PATH, "No path to peer (PE %d's device heap is not mapped: SHMEMX_TRANSPORT=p2p or "
                "both maps it)", op->pe);
@@ -142,11 +146,6 @@ extern "C" int sos_rma_check(const sos_rma_layout *l, const sos_rma_op *op, char
 
 namespace {
 
-struct Layout {
-    std::vector<sos_rma_region> regions;
-    sos_rma_layout l;
-};
-
 bool heap_mapped(const State &s)
 {
     if (!s.p2p_ready || s.peer_heap.size() != (size_t)s.n_pes) return false;
@@ -155,7 +154,9 @@ bool heap_mapped(const State &s)
     return true;
 }
 
-void layout_now(Layout &out)
+}  // namespace
+
+void sosrt::rma_layout_now(RmaLayout &out)
 {
     State &s = st();
     auto add = [&](const void *b, size_t n, int kind) {
@@ -172,16 +173,20 @@ void layout_now(Layout &out)
              out.regions.data()};
 }
 
+namespace {
+
 void checked(const sos_rma_op &op, const char *fn)
 {
-    Layout lay;
-    layout_now(lay);
+    RmaLayout lay;
+    rma_layout_now(lay);
     char msg[512];
     if (sos_rma_check(&lay.l, &op, msg, sizeof(msg)) != SOS_RMA_OK) raise_error("%s: %s", fn, msg);
 }
 
+}  // namespace
+
 // the remote side's address on this PE
-char *translate(const void *remote, int pe)
+char *sosrt::translate(const void *remote, int pe)
 {
     State &s = st();
     if (pe == s.my_pe) return (char *)remote;
@@ -190,7 +195,7 @@ char *translate(const void *remote, int pe)
 
 // Before a launch or copy that reads peer `pe`'s heap: the acquire a wait since the last
 // one left owed, and the read counted.
-void before_peer_read(int pe, const char *fn)
+void sosrt::before_peer_read(int pe, const char *fn)
 {
     State &s = st();
     if (pe == s.my_pe) return;
@@ -203,7 +208,7 @@ void before_peer_read(int pe, const char *fn)
 // such as a data segment whose first page was rounded off).  Device memory is its own
 // address; host memory that HIP allocated or registered is reached through the device
 // pointer HIP reports for it (hipHostGetDevicePointer's), which need not equal p.
-char *device_view(const void *p, size_t bytes)
+char *sosrt::device_view(const void *p, size_t bytes)
 {
     if (is_device_ptr(p)) return (char *)p;
     hipPointerAttribute_t a, z;
@@ -218,6 +223,8 @@ char *device_view(const void *p, size_t bytes)
     if ((char *)z.devicePointer - (char *)a.devicePointer != (ptrdiff_t)(bytes - 1)) return nullptr;
     return (char *)a.devicePointer;
 }
+
+namespace {
 
 void contiguous(void *dst, const void *src, size_t bytes, int read_pe, bool nbi, const char *fn)
 {

@@ -248,6 +248,8 @@ size_t small_path_set_device_bytes(size_t team_bytes);
 bool small_local_combine(int op, int dt, void *inout, const void *in, size_t count, size_t ts,
                          bool dev_io, bool dev_in);
 void small_local_release();
+// frees the atomics' pinned result word and nbi ring (amo.cpp; shmem_finalize)
+void amo_release();
 void team_word_put(int which, int world_pe, uint64_t v);   // node shm (p2p.cpp)
 uint64_t team_word_get(int which, int world_pe);
 // p2p signalling mode (p2p.cpp): stream-ordered device signals on the registered shm

@@ -102,6 +102,12 @@ _RUNTIME = {
                                            _c.c_size_t, _c.c_size_t, _c.c_void_p]),
     "sosx_block_copy_plan": (_c.c_int, [_c.c_void_p, _c.c_ssize_t, _c.c_void_p, _c.c_ssize_t, _c.c_size_t,
                                         _c.c_size_t, _c.c_size_t, _c.POINTER(_c.c_longlong)]),
+    # atomic memory operations: the generic entry, its checks and the kernel's C ABI (amo.cpp, amo.hip)
+    "sos_api_amo": (None, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t,
+                           _c.c_int, _c.c_int, _c.c_int, _c.c_char_p]),
+    "sos_amo_check": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_char_p, _c.c_size_t]),
+    "sosx_amo": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_size_t, _c.c_int,
+                            _c.c_void_p]),
     "sosx_prof_enable": (None, [_c.c_int]),
     "sosx_prof_get": (None, [_c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                              _c.POINTER(_c.c_long), _c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
@@ -114,6 +120,12 @@ _COLLECT_RE = re.compile(r"^shmem_(\w+?)_(fcollect|alltoalls|alltoall|collect)$"
 # shmem_<T>_put / get / put_nbi / get_nbi / iput / iget / p / g, shmem_put<N> ..., putmem / getmem,
 # shmemx_<T>_ibput / ibget and shmemx_ibput<N> / ibget<N>
 _RMA_RE = re.compile(r"^shmemx?_(?:(\w+?)_)?(ibput|ibget|iput|iget|put|get|p|g)(\d+|mem)?(_nbi)?$")
+# shmem_<T>_atomic_<op>[_nbi] and the deprecated shmem_<T>_<cswap|finc|inc|fadd|add|swap|fetch|set>
+_AMO_RE = re.compile(r"^shmem_(\w+?)_(?:atomic_(compare_swap|fetch_inc|inc|fetch_add|add|swap|fetch|set|and|or|xor|"
+                     r"fetch_and|fetch_or|fetch_xor)(_nbi)?|(cswap|finc|inc|fadd|add|swap|fetch|set))$")
+_AMO_OLD = {"cswap": "compare_swap", "finc": "fetch_inc", "fadd": "fetch_add"}
+_AMO_TYPES = ("int", "long", "longlong", "uint", "ulong", "ulonglong", "int32", "int64", "uint32", "uint64",
+              "size", "ptrdiff", "float", "double")
 _BY_VALUE = {"char": _c.c_char, "schar": _c.c_byte, "short": _c.c_short, "int": _c.c_int, "long": _c.c_long,
              "longlong": _c.c_longlong, "uchar": _c.c_ubyte, "ushort": _c.c_ushort, "uint": _c.c_uint,
              "ulong": _c.c_ulong, "ulonglong": _c.c_ulonglong, "int8": _c.c_int8, "int16": _c.c_int16,
@@ -182,6 +194,19 @@ def __getattr__(name):
         return fn
     if name in _RUNTIME:
         return getattr(L, name)
+    m = _AMO_RE.match(name)
+    if m and m.group(1) in _AMO_TYPES:
+        # values by value (float and double included); the nbi forms take `fetch` first and
+        # return nothing; the fetching forms return the old value
+        ty = _BY_VALUE[m.group(1)]
+        form = m.group(2) or _AMO_OLD.get(m.group(4), m.group(4))
+        nbi = bool(m.group(3))
+        fn = getattr(L, name)
+        operands = {"compare_swap": [ty, ty], "fetch_inc": [], "inc": [], "fetch": []}.get(form, [ty])
+        fetching = form in ("compare_swap", "swap", "fetch") or form.startswith("fetch_")
+        fn.restype = ty if fetching and not nbi else None
+        fn.argtypes = ([_c.c_void_p] if nbi else []) + [_c.c_void_p] + operands + [_c.c_int]
+        return fn
     m = _RMA_RE.match(name)
     if m and (m.group(1) is None or m.group(1) in _BY_VALUE):
         ty, kind = m.group(1), m.group(2)
