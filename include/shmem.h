@@ -155,4 +155,10 @@ int pshmem_broadcastmem(shmem_team_t team, void *dest, const void *source, size_
 /* ---- atomic memory operations shmem_<T>_atomic_* (generated) ---------------- */
 #include "shmem_amo.h"
 
+/* ---- put with signal, signal operations (generated) ------------------------- */
+#include "shmem_signal.h"
+
+/* ---- point-to-point synchronisation: wait_until, test (generated) ----------- */
+#include "shmem_sync.h"
+
 #endif /* SHMEM_H */

@@ -250,6 +250,43 @@ int sosx_block_copy_plan(uintptr_t dst, ptrdiff_t dst_stride, uintptr_t src, ptr
 int sosx_amo(int op, void *target, uint64_t value, uint64_t cond, void *fetch, size_t width,
              int is_float, void *stream);
 
+/* ---- put with signal, point-to-point waits (shmem_put_signal, shmem_wait_until) ---- */
+#define SOSX_SIGNAL_SET 0  /* SHMEM_SIGNAL_SET */
+#define SOSX_SIGNAL_ADD 1  /* SHMEM_SIGNAL_ADD */
+
+/* One launch, async on `stream`: copy nbytes from source to target, then update the 64-bit
+ * word at sig_addr -- a system-scope exchange with `signal` (SET) or fetch_add of it (ADD)
+ * -- no earlier than the payload is visible system-wide.  nbytes 0 only updates the
+ * signal.  All addresses are device-reachable; sig_addr is a multiple of 8.  The launches
+ * share one ticket word in device memory and must be serial (one stream at a time).
+ * Arguments are checked before any device work (SOSX_ERR_ARG: a null pointer, a misaligned
+ * sig_addr, an unknown sig_op). */
+int sosx_put_signal(void *target, const void *source, size_t nbytes, uint64_t *sig_addr, uint64_t signal,
+                    int sig_op, void *stream);
+/* The split that call would use (sos_amd/csrc/putsignal_plan.h): out = access width,
+ * unaligned loads, head bytes, body accesses, tail bytes, tiles, workgroups, the most
+ * workgroups any call uses.  Host only. */
+int sosx_put_signal_plan(uintptr_t target, uintptr_t source, size_t nbytes, long long out[8]);
+/* The ticket word (device memory; NULL before the first launch) and its release
+ * (shmem_finalize calls it).  Introspection for tests. */
+void *sosx_put_signal_ticket(void);
+void sosx_put_signal_release(void);
+
+/* shmem_put_signal takes the fused launch for payloads of at most this many bytes
+ * (SHMEMX_PUT_SIGNAL_FUSED_MAX sets the start value; 0: always composed of put, release
+ * and atomic).  Local switch; returns the previous limit. */
+size_t sosx_set_put_signal_fused_max(size_t bytes);
+/* How many shmem_put_signal calls were fused / composed, and how many probes the waits and
+ * tests ran.  Any pointer may be null.  Introspection for tests. */
+void sosx_signal_stats(long *fused, long *composed, long *probes);
+
+/* Copy nelems words of `width` (2, 4 or 8) bytes from device-reachable `ivars` to `out`
+ * (the device view of pinned host memory), async on `stream`: each word is read once with
+ * a relaxed system-scope atomic load.  The host reads `out` after the stream's next
+ * system-scope release.  Arguments are checked before any device work; nelems 0 is a
+ * no-op. */
+int sosx_sync_snapshot(void *out, const void *ivars, size_t nelems, size_t width, void *stream);
+
 /* p2p transport signalling (internal): store wval[i] to waddr[i] (i < nw) in stream
  * order, then wait until *qaddr[i] >= qval[i] (i < nq); a wait longer than limit_ticks
  * of the device wall clock sets *err and gives up.  Addresses are device views of

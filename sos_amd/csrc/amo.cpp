@@ -22,7 +22,9 @@
 //  * visibility, consumer half: a fetching operation on a peer's heap reads it, and
 //    follows the acquire a wait may have left owed (before_peer_read, as get does).
 //
-// There is no wait on memory anywhere: no spin in a kernel, no host polling loop.
+// There is no wait on memory in this file: no spin in a kernel, no host polling loop.  The
+// point-to-point waits (shmem_wait_until, shmem_test, shmem_signal_wait_until) are
+// signal.cpp's: host-driven probes under a wall-clock bound, never a spin on the GPU.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>

@@ -126,6 +126,62 @@ typedef struct {
 } sos_amo_op;
 int sos_amo_check(const sos_rma_layout *layout, const sos_amo_op *op, char *msg, size_t msg_len);
 
+// ---- put with signal, signal operations, point-to-point waits (signal.cpp) ---------------
+// SHMEM_DEF_PUT_SIGNAL / _NBI and the sized and mem forms (src/data_c.c4:684-784)
+void sos_api_put_signal(void *dest, const void *source, size_t nelems, size_t type_size, uint64_t *sig_addr,
+                        uint64_t signal, int sig_op, int pe, int nbi, const char *fn);
+// shmemx_signal_set / shmemx_signal_add: sig_op on a peer's (or the caller's) signal word
+void sos_api_signal_op(uint64_t *sig_addr, uint64_t signal, int sig_op, int pe, const char *fn);
+// shmem_signal_fetch: the calling PE's own word
+uint64_t sos_api_signal_fetch(const uint64_t *sig_addr, const char *fn);
+// The kinds of a wait or test: one ivar, or the _all / _any / _some forms over nelems.
+enum { SOS_SYNC_ONE = 0, SOS_SYNC_ALL = 1, SOS_SYNC_ANY = 2, SOS_SYNC_SOME = 3 };
+// shmem_<T>_wait_until[_all|_any|_some][_vector] (src/synchronization_c.c4:203-481): returns
+// when the comparison holds -- for ONE and ALL 0, for ANY the index (SIZE_MAX: nothing to
+// wait for), for SOME the count with `indices` filled.  `value` points at one value, or at
+// nelems of them (vector).  *satisfied (or NULL) receives the ivar's value that satisfied a
+// ONE wait (shmem_signal_wait_until).  cmp < 0: the deprecated shmem_<T>_wait, "until the
+// ivar differs from value" (SHMEM_CMP_NE without the comparison check).
+size_t sos_api_wait(void *ivars, size_t nelems, size_t *indices, const int *status, int cmp, const void *value,
+                    int vector, int kind, size_t type_size, int is_signed, uint64_t *satisfied, const char *fn);
+// shmem_<T>_test[_all|_any|_some][_vector] (:484-735): ONE probe; ONE and ALL return 0 / 1.
+size_t sos_api_test(void *ivars, size_t nelems, size_t *indices, const int *status, int cmp, const void *value,
+                    int vector, int kind, size_t type_size, int is_signed, const char *fn);
+
+// Their checks as plain functions over the layout struct of sos_rma_check: 0, or a code
+// with a message that names the argument.  SOS's refusals in SOS's order, then this
+// library's own.
+enum { SOS_SIG_BAD_OP = 12,    // sig_op is neither SHMEM_SIGNAL_SET nor SHMEM_SIGNAL_ADD
+       SOS_SYNC_BAD_CMP = 13 };  // the comparison is none of SHMEM_CMP_*
+typedef struct {
+    const void *target, *source, *sig_addr;
+    size_t nelems, type_size;
+    int sig_op;
+    int pe;
+} sos_put_signal_op;
+int sos_put_signal_check(const sos_rma_layout *layout, const sos_put_signal_op *op, char *msg, size_t msg_len);
+typedef struct {
+    const void *ivars;
+    size_t nelems, type_size;  // ONE: nelems is 1
+    const void *status;        // const int[nelems] or NULL (ALL / ANY / SOME)
+    const void *indices;       // size_t[nelems] (SOME)
+    int kind;                  // SOS_SYNC_*
+    int cmp;
+} sos_sync_op;
+int sos_sync_check(const sos_rma_layout *layout, const sos_sync_op *op, char *msg, size_t msg_len);
+
+// The comparison of a wait or test over a snapshot of the ivars, as SOS's macros make it
+// (SHMEM_TEST and the loops of src/synchronization_c.c4): `snapshot` holds nelems words of
+// `width` (2, 4 or 8) bytes, compared signed or unsigned at that width against *value (or
+// value[i], vector) for every i with status NULL or status[i] == 0.
+//   ONE / ALL: returns 1 when (every unmasked) comparison holds;
+//   ANY: returns 1 and *index = the lowest satisfied unmasked index, else *index = SIZE_MAX;
+//   SOME: *count = how many hold, their indices ascending in `indices`; returns count > 0.
+// nelems == 0 or everything masked: returns 1 (a wait returns at once) with
+// *index = SIZE_MAX and *count = 0.  -1 for an argument it cannot use.
+int sos_sync_eval(const void *snapshot, size_t nelems, size_t width, int is_signed, const int *status, int cmp,
+                  const void *value, int vector, int kind, size_t *index, size_t *indices, size_t *count);
+
 #ifdef __cplusplus
 }
 

@@ -38,6 +38,15 @@ makes their min/max compare signed -- and writes:
                                   (mpp/shmem_c_func.h4:243-404, :575-639)
   sos_amd/csrc/amo_gen.cpp        their definitions (src/atomic_c.c4) over amo.cpp
 
+  include/shmem_signal.h          put with signal shmem_<T>_put_signal[_nbi], the sized and mem forms,
+                                  shmem_signal_fetch, shmemx_signal_add / _set, generics and
+                                  overloads (mpp/shmem_c_func.h4:91-127, mpp/shmemx_c_func.h4:98-100)
+  include/shmem_sync.h            shmem_<T>_wait_until / _test with their _all / _any / _some and
+                                  _vector forms, shmem_signal_wait_until, the deprecated waits
+                                  (mpp/shmem_c_func.h4:473-542)
+  sos_amd/csrc/signal_gen.cpp     their definitions (src/data_c.c4:684-784,
+                                  src/synchronization_c.c4) over signal.cpp
+
 The library's Makefile compiles every *.cpp of the directory, so a new generated source
 needs no entry there.
 
@@ -691,6 +700,224 @@ def amo_source():
     return "\n".join(out)
 
 
+# ---- put with signal, signal operations, point-to-point synchronisation
+# (mpp/shmem_c_func.h4:91-127, :473-542, :705; mpp/shmemx_c_func.h4:98-100;
+# bindings/shmem_bind_c.m4:71-91; src/data_c.c4:684-784, src/synchronization_c.c4).  There are
+# no contexts: the shmem_ctx_* forms are not provided.
+WAIT = [("short", "short"), ("int", "int"), ("long", "long"), ("longlong", "long long")]
+SYNC = WAIT + [("ushort", "unsigned short"), ("uint", "unsigned int"), ("ulong", "unsigned long"),
+               ("ulonglong", "unsigned long long"), ("int32", "int32_t"), ("int64", "int64_t"),
+               ("uint32", "uint32_t"), ("uint64", "uint64_t"), ("size", "size_t"), ("ptrdiff", "ptrdiff_t")]
+_SYNC_SIGNED = {"short", "int", "long", "longlong", "int32", "int64", "ptrdiff"}
+# the generic selectors' arms (bindings/shmem_bind_c11.m4:58-67, shmem_bind_cxx.m4:56-63)
+SYNC_GENERIC_C11 = SYNC[:8]
+SYNC_GENERIC_CXX = [t for t in SYNC[:8] if t[0] not in ("short", "ushort")]
+# form -> (return type, kind, has indices, vector)
+SYNC_FORMS = {}
+for _w, _wret in (("wait_until", None), ("test", "int")):
+    SYNC_FORMS[_w] = (_wret or "void", "ONE", False, False)
+    for _vec in (False, True):
+        _sfx = "_vector" if _vec else ""
+        SYNC_FORMS[f"{_w}_all{_sfx}"] = (_wret or "void", "ALL", False, _vec)
+        SYNC_FORMS[f"{_w}_any{_sfx}"] = ("size_t", "ANY", False, _vec)
+        SYNC_FORMS[f"{_w}_some{_sfx}"] = ("size_t", "SOME", True, _vec)
+_PUT_SIGNAL_ARGS = "size_t nelems, uint64_t *sig_addr, uint64_t signal, int sig_op, int pe"
+_PUT_SIGNAL_NAMES = "nelems, sig_addr, signal, sig_op, pe"
+
+
+def _sync_params(form, ct):
+    """(parameter list, argument names) of one wait / test form for C type `ct`."""
+    ret, kind, has_idx, vec = SYNC_FORMS[form]
+    if kind == "ONE":
+        return f"{ct} *var, int cmp, {ct} value", "var, cmp, value"
+    idx = "size_t *indices, " if has_idx else ""
+    val = f"{ct} *values" if vec else f"{ct} value"
+    return (f"{ct} *vars, size_t nelems, {idx}const int *status, int cmp, {val}",
+            f"vars, nelems, {'indices, ' if has_idx else ''}status, cmp, {'values' if vec else 'value'}")
+
+
+def _sync_macro(form):
+    return "SOS_" + form.upper()
+
+
+def _sync_call(form, ct, signed, name):
+    """The body of one wait / test form: `ct`, `signed` and `name` as C expressions."""
+    ret, kind, has_idx, vec = SYNC_FORMS[form]
+    ivars = "var, 1" if kind == "ONE" else "vars, nelems"
+    common = (f"{ivars}, {'indices' if has_idx else 'NULL'}, {'NULL' if kind == 'ONE' else 'status'}, cmp, "
+              f"{'values' if vec else '&value'}, {1 if vec else 0}, SOS_SYNC_{kind}, sizeof({ct}), {signed}")
+    call = f"sos_api_wait({common}, NULL, {name});" if form.startswith("wait") else f"sos_api_test({common}, {name});"
+    return call if ret == "void" else f"return {'(int)' if ret == 'int' else ''}{call}"
+
+
+def signal_entries():
+    """(header section, name, sig(prefix), source line, deprecated, guard) of every generated
+    put-with-signal, signal and point-to-point synchronisation entry.  source line: the
+    entry's one line in signal_gen.cpp, an invocation of SOS_ENTRY or of its family's macro
+    (signal_macros); guard: a preprocessor condition under which the header declares it."""
+    out = []
+
+    def add(sec, name, ret, params, body=None, line=None, dep=False, guard=None):
+        proto = f"{ret} {{p}}{name}({params})"
+        out.append((sec, name, lambda p, proto=proto: proto.format(p=p),
+                    line or f"SOS_ENTRY({ret}, {name}, ({params}), {body})", dep, guard))
+
+    def put_signal(name, ct, size, nbi):
+        add("signal", name, "void", f"{ct} *target, const {ct} *source, {_PUT_SIGNAL_ARGS}",
+            line=f"SOS_PUT_SIGNAL({name}, {ct}, {size}, {nbi})")
+
+    for nbi, sfx in ((0, ""), (1, "_nbi")):
+        for st, ct in RMA:
+            put_signal(f"shmem_{st}_put_signal{sfx}", ct, f"sizeof({ct})", nbi)
+        for bits in RMA_SIZES:
+            put_signal(f"shmem_put{bits}_signal{sfx}", "void", str(bits // 8), nbi)
+        put_signal(f"shmem_putmem_signal{sfx}", "void", "1", nbi)
+    add("signal", "shmem_signal_fetch", "uint64_t", "const uint64_t *sig_addr",
+        'return sos_api_signal_fetch(sig_addr, "shmem_signal_fetch");')
+    for op in ("add", "set"):
+        name = f"shmemx_signal_{op}"
+        add("signal", name, "void", "uint64_t *sig_addr, uint64_t signal, int pe",
+            f'sos_api_signal_op(sig_addr, signal, SOSX_SIGNAL_{op.upper()}, pe, "{name}");')
+    # the deprecated waits: until the ivar differs from value (cmp -1)
+    for st, ct in WAIT:
+        add("sync", f"shmem_{st}_wait", "void", f"{ct} *var, {ct} value", line=f"SOS_WAIT(shmem_{st}_wait, {ct})", dep=True)
+    add("sync", "shmem_wait", "void", "long *ivar, long cmp_value",
+        'sos_api_wait(ivar, 1, NULL, NULL, -1, &cmp_value, 0, SOS_SYNC_ONE, sizeof(long), 1, NULL, "shmem_wait");',
+        dep=True)
+    # "Special case, only enabled when C++ and C11 bindings are disabled".  signal_gen.cpp is
+    # C++, where the header's overloads hold the name: the weak alias gets its symbol name
+    # from an asm label
+    add("sync", "shmem_wait_until", "void", "long *ivar, int cmp, long value",
+        line='void pshmem_wait_until(long *ivar, int cmp, long value) { sos_api_wait(ivar, 1, NULL, NULL, cmp, &value, 0, '
+             'SOS_SYNC_ONE, sizeof(long), 1, NULL, "shmem_wait_until"); }\n'
+             'void sos_untyped_wait_until(long *ivar, int cmp, long value) __asm__("shmem_wait_until") '
+             '__attribute__((weak, alias("pshmem_wait_until")));',
+        guard="(!defined(__cplusplus) && !(defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L)) || "
+              "defined(SHMEM_DECLARE_SPECIAL_CASES)")
+    for form, (ret, kind, has_idx, vec) in SYNC_FORMS.items():
+        for st, ct in SYNC:
+            name = f"shmem_{st}_{form}"
+            add("sync", name, ret, _sync_params(form, ct)[0],
+                line=f"{_sync_macro(form)}({name}, {ct}, {1 if st in _SYNC_SIGNED else 0})")
+    add("sync", "shmem_signal_wait_until", "uint64_t", "uint64_t *sig_addr, int cmp, uint64_t cmp_value",
+        'uint64_t got = 0; sos_api_wait(sig_addr, 1, NULL, NULL, cmp, &cmp_value, 0, SOS_SYNC_ONE, sizeof(uint64_t), '
+        '0, &got, "shmem_signal_wait_until"); return got;')
+    return out
+
+
+def signal_macros():
+    """The macros signal_gen.cpp's lines invoke: SOS_ENTRY (the strong pshmem form with its
+    one-line body and the weak alias) and one macro per family over (name, C type, ...)."""
+    out = ["#define SOS_ENTRY(ret, name, params, ...) \\",
+           "    ret p##name params { __VA_ARGS__ } \\",
+           "    ret name params __attribute__((weak, alias(\"p\" #name)));",
+           "#define SOS_PUT_SIGNAL(name, T, size, nbi) \\",
+           f"    SOS_ENTRY(void, name, (T *target, const T *source, {_PUT_SIGNAL_ARGS}), \\",
+           "              sos_api_put_signal(target, source, nelems, size, sig_addr, signal, sig_op, pe, nbi, #name);)",
+           "#define SOS_WAIT(name, T) \\",
+           "    SOS_ENTRY(void, name, (T *var, T value), \\",
+           "              sos_api_wait(var, 1, NULL, NULL, -1, &value, 0, SOS_SYNC_ONE, sizeof(T), 1, NULL, #name);)"]
+    for form, (ret, kind, has_idx, vec) in SYNC_FORMS.items():
+        out += [f"#define {_sync_macro(form)}(name, T, sg) \\",
+                f"    SOS_ENTRY({ret}, name, ({_sync_params(form, 'T')[0]}), \\",
+                f"              {_sync_call(form, 'T', 'sg', '#name')})"]
+    return out
+
+
+def signal_symbols():
+    """Every public put-with-signal, signal and point-to-point synchronisation name."""
+    return [name for _, name, _, _, _, _ in signal_entries()]
+
+
+def _signal_generics(sec):
+    out = ["#if defined(__cplusplus)"]
+    if sec == "signal":
+        for sfx in ("", "_nbi"):
+            for st, ct in GENERIC_RMA:
+                out.append(f"static inline void shmem_put_signal{sfx}({ct} *dest, const {ct} *source, "
+                           f"{_PUT_SIGNAL_ARGS}) {{ shmem_{st}_put_signal{sfx}(dest, source, {_PUT_SIGNAL_NAMES}); }}")
+    else:
+        for form, (ret, kind, has_idx, vec) in SYNC_FORMS.items():
+            for st, ct in SYNC_GENERIC_CXX:
+                params, names = _sync_params(form, ct)
+                out.append(f"static inline {ret} shmem_{form}({params}) "
+                           f"{{ {'return ' if ret != 'void' else ''}shmem_{st}_{form}({names}); }}")
+    out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
+    out += c11_prelude()
+    out += ["#ifndef SHMEM_C11_ARG0", "#define SHMEM_C11_ARG0(...) SHMEM_C11_ARG0_HELPER(__VA_ARGS__, sentinel)",
+            "#define SHMEM_C11_ARG0_HELPER(first, ...) first", "#endif"]
+    if sec == "signal":
+        for sfx in ("", "_nbi"):
+            out += c11_generic(f"shmem_put_signal{sfx}",
+                               [f"        {ct}*: shmem_{st}_put_signal{sfx}" for st, ct in GENERIC_RMA], argidx=0)
+    else:
+        for form in SYNC_FORMS:
+            out += c11_generic(f"shmem_{form}", [f"        {ct}*: shmem_{st}_{form}" for st, ct in SYNC_GENERIC_C11],
+                               argidx=0)
+    out.append("#endif")
+    return out
+
+
+def signal_header(sec):
+    fname = "shmem_signal.h" if sec == "signal" else "shmem_sync.h"
+    guard = fname.upper().replace(".", "_")
+    out = [f"/* {fname} -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", " *"]
+    if sec == "signal":
+        out += [" * SOS's put with signal on the device symmetric heap: shmem_<T>_put_signal[_nbi] over the",
+                " * 24 RMA types, the sized forms for 8..128 bits, putmem_signal[_nbi], shmem_signal_fetch",
+                " * and SOS's extensions shmemx_signal_add / shmemx_signal_set (mpp/shmem_c_func.h4:91-127,",
+                " * :705; mpp/shmemx_c_func.h4:98-100), with the C11 generic selectors and the C++ overloads.",
+                " * There are no contexts: the shmem_ctx_* forms are not provided.  Included from shmem.h. */"]
+    else:
+        out += [" * SOS's point-to-point synchronisation (mpp/shmem_c_func.h4:473-542): shmem_<T>_wait_until",
+                " * and shmem_<T>_test with their _all / _any / _some and _vector forms over the 14 SYNC",
+                " * types, shmem_signal_wait_until, and the deprecated shmem_<T>_wait over short, int, long,",
+                " * long long; the C11 generic selectors and the C++ overloads.  The untyped shmem_wait_until",
+                " * is declared where SOS declares it: not under the C11 or C++ generics.  Included from",
+                " * shmem.h. */"]
+    out += [f"#ifndef {guard}", f"#define {guard}", ""]
+    if sec == "signal":
+        out += ["/* signal operations (mpp/shmem-def.h.in:116-117) */", "#define SHMEM_SIGNAL_SET 0",
+                "#define SHMEM_SIGNAL_ADD 1", ""]
+    else:
+        out += ["/* comparisons (mpp/shmem-def.h.in:27-39) */"]
+        for i, c in enumerate(("EQ", "NE", "GT", "GE", "LT", "LE")):
+            out += [f"#define SHMEM_CMP_{c} {i + 1}", f"#define _SHMEM_CMP_{c} {i + 1}"]
+        out += ["", "#ifndef SHMEM_ATTRIBUTE_DEPRECATED",
+                "#define SHMEM_ATTRIBUTE_DEPRECATED __attribute__((deprecated))", "#endif", ""]
+    out += ["#ifdef __cplusplus", 'extern "C" {', "#endif", ""]
+    entries = [e for e in signal_entries() if e[0] == sec]
+
+    def declare(attr, prefix):
+        for _, name, sig, _, dep, cond in entries:
+            line = f"{attr}{sig(prefix)}{' SHMEM_ATTRIBUTE_DEPRECATED' if dep else ''};"
+            out.extend([f"#if {cond}", line, "#endif"] if cond else [line])
+
+    declare("SHMEM_FUNCTION_ATTRIBUTES ", "")
+    out += ["", "/* profiling interface: pshmem_* are the implementations, shmem_* weak aliases */"]
+    declare("", "p")
+    out += ["", "#ifdef __cplusplus", "}  /* extern \"C\" */", "#endif", ""]
+    out += _signal_generics(sec)
+    out += ["", f"#endif /* {guard} */", ""]
+    return "\n".join(out)
+
+
+def signal_source():
+    out = ["// signal_gen.cpp -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", "//",
+           "// Put with signal, the signal operations and the point-to-point waits and tests",
+           "// (SHMEM_DEF_PUT_SIGNAL ... _PUT_N_SIGNAL_NBI over SHMEM_BIND_C_RMA and SHMEM_BIND_C_SIZES,",
+           "// src/data_c.c4:684-784; SHMEM_DEF_WAIT ... SHMEM_DEF_TEST_SOME_VECTOR over SHMEM_BIND_C_WAIT",
+           "// and SHMEM_BIND_C_SYNC, src/synchronization_c.c4) over signal.cpp: strong pshmem_*, weak",
+           "// shmem_* aliases.  One line per entry point: the families stamp theirs out of a macro per",
+           "// form, as SOS stamps its own out of SHMEM_DEF_* macros over its type tables.",
+           '#include "shmem.h"', '#include "sosx.h"', '#include "api_internal.h"', ""]
+    out += signal_macros()
+    out += ["", 'extern "C" {', ""]
+    out += [line for _, _, _, line, _, _ in signal_entries()]
+    out += ["", '}  // extern "C"', ""]
+    return "\n".join(out)
+
+
 def collect_symbols():
     """The generated fcollect / alltoall / alltoalls names (typed forms only)."""
     return [f"shmem_{st}_{kind}" for kind in COLLECTS for st, ct in RMA]
@@ -727,6 +954,11 @@ def main():
     assert len(amo_symbols()) == len(set(amo_symbols())) == n_amo, (len(amo_symbols()), n_amo)
     targets[os.path.join(ROOT, "include", "shmem_amo.h")] = amo_header()
     targets[os.path.join(ROOT, "sos_amd", "csrc", "amo_gen.cpp")] = amo_source()
+    n_sig = 2 * (len(RMA) + len(RMA_SIZES) + 1) + 4 + len(SYNC) * len(SYNC_FORMS) + len(WAIT) + 2
+    assert len(signal_symbols()) == len(set(signal_symbols())) == n_sig == 266, (len(signal_symbols()), n_sig)
+    targets[os.path.join(ROOT, "include", "shmem_signal.h")] = signal_header("signal")
+    targets[os.path.join(ROOT, "include", "shmem_sync.h")] = signal_header("sync")
+    targets[os.path.join(ROOT, "sos_amd", "csrc", "signal_gen.cpp")] = signal_source()
     check = "--check" in sys.argv
     stale = False
     for path, text in targets.items():

@@ -37,23 +37,7 @@ using namespace sosrt;
 extern "C" char __data_start[] __attribute__((weak));
 extern "C" char _end[] __attribute__((weak));
 
-namespace sosrt {
-
-const sos_rma_region *rma_find_region(const sos_rma_layout *l, uintptr_t p)
-{
-    for (int i = 0; i < l->nregions; ++i)
-        if (p >= l->regions[i].base && p - l->regions[i].base < l->regions[i].size) return &l->regions[i];
-    return nullptr;
-}
-
-const char *rma_region_name(int kind)
-{
-    return kind == SOS_RMA_REGION_HOST_HEAP ? "sym. heap region"
-           : kind == SOS_RMA_REGION_DEVICE_HEAP ? "device sym. heap region"
-           : kind == SOS_RMA_REGION_DATA ? "sym. data region" : "device allocation";
-}
-
-}  // namespace sosrt
+// rma_find_region and rma_region_name live in signal_checks.cpp, the file without HIP
 
 namespace {
 

@@ -895,6 +895,7 @@ void shmem_finalize(void)
     sosx_combine_host_release();
     small_local_release();
     amo_release();
+    signal_release();
     if (s.collect_lens) (void)hipHostFree(s.collect_lens);
     s.collect_lens = nullptr;
     if (s.stripes) (void)hipFree(s.stripes);

@@ -250,6 +250,8 @@ bool small_local_combine(int op, int dt, void *inout, const void *in, size_t cou
 void small_local_release();
 // frees the atomics' pinned result word and nbi ring (amo.cpp; shmem_finalize)
 void amo_release();
+// frees the waits' pinned snapshot buffer and put-with-signal's ticket word (signal.cpp)
+void signal_release();
 void team_word_put(int which, int world_pe, uint64_t v);   // node shm (p2p.cpp)
 uint64_t team_word_get(int which, int world_pe);
 // p2p signalling mode (p2p.cpp): stream-ordered device signals on the registered shm

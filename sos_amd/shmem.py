@@ -108,6 +108,33 @@ _RUNTIME = {
     "sos_amo_check": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_char_p, _c.c_size_t]),
     "sosx_amo": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_size_t, _c.c_int,
                             _c.c_void_p]),
+    # put with signal, signal operations, waits and tests: the generic entries, their checks, the
+    # comparison and the kernels' C ABI (signal.cpp, signal_checks.cpp, putsignal.hip)
+    "sos_api_put_signal": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p, _c.c_uint64,
+                                  _c.c_int, _c.c_int, _c.c_int, _c.c_char_p]),
+    "sos_api_signal_op": (None, [_c.c_void_p, _c.c_uint64, _c.c_int, _c.c_int, _c.c_char_p]),
+    "sos_api_signal_fetch": (_c.c_uint64, [_c.c_void_p, _c.c_char_p]),
+    "sos_api_wait": (_c.c_size_t, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                   _c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_char_p]),
+    "sos_api_test": (_c.c_size_t, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                   _c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_char_p]),
+    "sos_put_signal_check": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_char_p, _c.c_size_t]),
+    "sos_sync_check": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_char_p, _c.c_size_t]),
+    "sos_sync_eval": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_int,
+                                 _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "sosx_put_signal": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_uint64, _c.c_int,
+                                   _c.c_void_p]),
+    "sosx_put_signal_plan": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_longlong)]),
+    "sosx_put_signal_ticket": (_c.c_void_p, []),
+    "sosx_set_put_signal_fused_max": (_c.c_size_t, [_c.c_size_t]),
+    "sosx_signal_stats": (None, [_c.POINTER(_c.c_long), _c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
+    "sosx_sync_snapshot": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p]),
+    "shmem_signal_fetch": (_c.c_uint64, [_c.c_void_p]),
+    "shmemx_signal_add": (None, [_c.c_void_p, _c.c_uint64, _c.c_int]),
+    "shmemx_signal_set": (None, [_c.c_void_p, _c.c_uint64, _c.c_int]),
+    "shmem_signal_wait_until": (_c.c_uint64, [_c.c_void_p, _c.c_int, _c.c_uint64]),
+    "shmem_wait": (None, [_c.c_void_p, _c.c_long]),
+    "shmem_wait_until": (None, [_c.c_void_p, _c.c_int, _c.c_long]),
     "sosx_prof_enable": (None, [_c.c_int]),
     "sosx_prof_get": (None, [_c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                              _c.POINTER(_c.c_long), _c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
@@ -126,6 +153,12 @@ _AMO_RE = re.compile(r"^shmem_(\w+?)_(?:atomic_(compare_swap|fetch_inc|inc|fetch
 _AMO_OLD = {"cswap": "compare_swap", "finc": "fetch_inc", "fadd": "fetch_add"}
 _AMO_TYPES = ("int", "long", "longlong", "uint", "ulong", "ulonglong", "int32", "int64", "uint32", "uint64",
               "size", "ptrdiff", "float", "double")
+# shmem_<T>_put_signal[_nbi], shmem_put<N>_signal[_nbi], shmem_putmem_signal[_nbi]
+_PUT_SIGNAL_RE = re.compile(r"^shmem_(?:(\w+?)_put|put(?:\d+|mem))_signal(_nbi)?$")
+# shmem_<T>_wait_until / _test with their _all / _any / _some and _vector forms, and the deprecated shmem_<T>_wait
+_SYNC_RE = re.compile(r"^shmem_(\w+?)_(?:(wait_until|test)(?:_(all|any|some))?(_vector)?|(wait))$")
+_SYNC_TYPES = ("short", "int", "long", "longlong", "ushort", "uint", "ulong", "ulonglong", "int32", "int64",
+               "uint32", "uint64", "size", "ptrdiff")
 _BY_VALUE = {"char": _c.c_char, "schar": _c.c_byte, "short": _c.c_short, "int": _c.c_int, "long": _c.c_long,
              "longlong": _c.c_longlong, "uchar": _c.c_ubyte, "ushort": _c.c_ushort, "uint": _c.c_uint,
              "ulong": _c.c_ulong, "ulonglong": _c.c_ulonglong, "int8": _c.c_int8, "int16": _c.c_int16,
@@ -194,6 +227,33 @@ def __getattr__(name):
         return fn
     if name in _RUNTIME:
         return getattr(L, name)
+    m = _PUT_SIGNAL_RE.match(name)
+    if m and (m.group(1) is None or m.group(1) in _BY_VALUE):
+        # (target, source, nelems, sig_addr, signal, sig_op, pe)
+        fn = getattr(L, name)
+        fn.restype = None
+        fn.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_int]
+        return fn
+    m = _SYNC_RE.match(name)
+    if m and m.group(1) in _SYNC_TYPES:
+        # the value by value, the _vector forms' values by address; _any / _some return a size_t,
+        # test and test_all an int, the waits nothing
+        ty = _BY_VALUE[m.group(1)]
+        fn = getattr(L, name)
+        if m.group(5):  # shmem_<T>_wait(var, value)
+            fn.restype, fn.argtypes = None, [_c.c_void_p, ty]
+            return fn
+        what, kind, vector = m.group(2), m.group(3), bool(m.group(4))
+        if kind is None:
+            if vector:
+                raise AttributeError(name)
+            fn.restype = _c.c_int if what == "test" else None
+            fn.argtypes = [_c.c_void_p, _c.c_int, ty]
+            return fn
+        fn.restype = _c.c_size_t if kind in ("any", "some") else (_c.c_int if what == "test" else None)
+        fn.argtypes = ([_c.c_void_p, _c.c_size_t] + ([_c.c_void_p] if kind == "some" else [])
+                       + [_c.c_void_p, _c.c_int, _c.c_void_p if vector else ty])
+        return fn
     m = _AMO_RE.match(name)
     if m and m.group(1) in _AMO_TYPES:
         # values by value (float and double included); the nbi forms take `fetch` first and
