@@ -161,4 +161,7 @@ int pshmem_broadcastmem(shmem_team_t team, void *dest, const void *source, size_
 /* ---- point-to-point synchronisation: wait_until, test (generated) ----------- */
 #include "shmem_sync.h"
 
+/* ---- distributed locks: set_lock, clear_lock, test_lock ---------------------- */
+#include "shmem_lock.h"
+
 #endif /* SHMEM_H */

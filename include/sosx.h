@@ -287,6 +287,40 @@ void sosx_signal_stats(long *fused, long *composed, long *probes);
  * no-op. */
 int sosx_sync_snapshot(void *out, const void *ivars, size_t nelems, size_t width, void *stream);
 
+/* ---- distributed locks (shmem_set_lock, shmem_test_lock, shmem_clear_lock) ---------- */
+#define SOSX_LOCK_ENQUEUE 0  /* set_lock up to its wait: own data = 0, swap last, link */
+#define SOSX_LOCK_TRY     1  /* test_lock: own data = 0, last from 0 to me + 1 or not at all */
+#define SOSX_LOCK_RELEASE 2  /* clear_lock: last from me + 1 to 0, else the hand-off */
+#define SOSX_LOCK_HANDOFF 3  /* the hand-off alone, once a PENDING release has seen NEXT */
+/* the status a step leaves in its record */
+#define SOSX_LOCK_ACQUIRED 0
+#define SOSX_LOCK_QUEUED   1  /* wait for bit 31 (SIGNAL) of own data */
+#define SOSX_LOCK_BUSY     2
+#define SOSX_LOCK_RELEASED 3
+#define SOSX_LOCK_HANDED   4
+#define SOSX_LOCK_PENDING  5  /* wait for bits 0-30 (NEXT) of own data, then run SOSX_LOCK_HANDOFF */
+#define SOSX_LOCK_CORRUPT  6  /* a value read is no PE id + 1: no peer word was touched */
+#define SOSX_LOCK_RESULT_BYTES 16  /* int32 prev, uint32 data, int32 status, int32 bad */
+
+/* One step of SOS's MCS queue lock (src/shmem_lock.h) in one launch, async on `stream`: one
+ * wave whose first lane runs a chain of at most four system-scope atomics on 32-bit words
+ * and then stores the 16-byte record at `result` (plain stores; the host reads it after the
+ * stream's next system-scope release).  last_word is the lock's first half on PE 0,
+ * my_data_word its second half on the calling PE `me`; PE q's second half is at
+ * table[q] + offset (table: n_pes entries in device-reachable memory).  A release or
+ * hand-off leaves own data zero, so a lock nobody holds is zero on every PE.  The kernel never
+ * waits: where the algorithm would, the status says for what.  A predecessor or successor
+ * read from the lock is checked against 1..n_pes before an address is formed from it.
+ * Arguments are checked before any device work (SOSX_ERR_ARG: an unknown kind, a null or
+ * misaligned pointer, offset no multiple of 4, me outside [0, n_pes)). */
+int sosx_lock_step(int kind, void *last_word, void *my_data_word, const uint64_t *table, uint64_t offset,
+                   int me, int n_pes, void *result, void *stream);
+/* The device table of heap bases the locks use and how many entries it has (NULL, 0 before
+ * shmem_init); how many lock kernels and wait probes ran.  Any pointer may be null.
+ * Introspection for tests. */
+const uint64_t *sosx_lock_table(int *entries);
+void sosx_lock_stats(long *steps, long *probes);
+
 /* p2p transport signalling (internal): store wval[i] to waddr[i] (i < nw) in stream
  * order, then wait until *qaddr[i] >= qval[i] (i < nq); a wait longer than limit_ticks
  * of the device wall clock sets *err and gives up.  Addresses are device views of

@@ -182,6 +182,26 @@ int sos_sync_check(const sos_rma_layout *layout, const sos_sync_op *op, char *ms
 int sos_sync_eval(const void *snapshot, size_t nelems, size_t width, int is_signed, const int *status, int cmp,
                   const void *value, int vector, int kind, size_t *index, size_t *indices, size_t *count);
 
+// ---- distributed locks (lock.cpp) --------------------------------------------------------
+// shmem_set_lock / shmem_clear_lock / shmem_test_lock (src/lock_c.c:44-65)
+void sos_api_set_lock(long *lock, const char *fn);
+void sos_api_clear_lock(long *lock, const char *fn);
+int sos_api_test_lock(long *lock, const char *fn);
+// Their check over the layout struct of sos_rma_check, the same on every PE: SOS's
+// (initialized, `lock` symmetric over sizeof(long)), then this library's own -- 8-byte
+// alignment; with more than one PE the lock must be in the device symmetric heap
+// (SOS_RMA_PEER_NOT_DEVICE_HEAP) and the heap mapped (SOS_RMA_NO_PATH).
+typedef struct {
+    const void *lock;
+} sos_lock_op;
+int sos_lock_check(const sos_rma_layout *layout, const sos_lock_op *op, char *msg, size_t msg_len);
+// The messages of a wait that ran out and of a lock word that holds no PE id + 1, as plain
+// functions.  awaited: 0 = SIGNAL (set_lock), 1 = NEXT (clear_lock).
+enum { SOS_LOCK_AWAIT_SIGNAL = 0, SOS_LOCK_AWAIT_NEXT = 1 };
+void sos_lock_expiry_message(const char *fn, const void *lock, int awaited, uint32_t data, double seconds, char *msg,
+                             size_t msg_len);
+void sos_lock_corrupt_message(const void *lock, int value, int n_pes, char *msg, size_t msg_len);
+
 #ifdef __cplusplus
 }
 

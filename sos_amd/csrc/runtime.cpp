@@ -435,6 +435,7 @@ void ensure_device_heap()
     s.peer_heap.assign((size_t)s.n_pes, nullptr);
     s.peer_heap[(size_t)s.my_pe] = base;
     s.p2p_ready = s.n_pes == 1;
+    lock_table_build();  // this PE's base; the peers' once they are mapped (below)
     if (!s.want_p2p || s.n_pes == 1) return;
     if (!s.hub.up) raise_error("SHMEMX_TRANSPORT=p2p needs the shmem_init bootstrap");
     // p2p-only mode cannot run without the mapping; in `both` mode a failure on any PE
@@ -501,6 +502,7 @@ void ensure_device_heap()
         return;
     }
     s.p2p_ready = true;
+    lock_table_build();
     debug_msg("device heap %zu B (stage %zu B) mapped on %d PEs", s.dev_heap_bytes,
               s.sym_stage_bytes, s.n_pes);
     p2p_signal_setup();
@@ -753,6 +755,7 @@ static void init_common(int pe, int npes, const ncclUniqueId *uid)
     s.finalized = false;
     register_data_segment(s);
     if (s.want_p2p || s.ext_base) ensure_device_heap();
+    lock_table_build();
     if (s.shm.extra && npes > 1)
         small_path_setup((char *)s.shm.extra + shm_p2p_region_bytes(), small_shared_bytes(npes));
     if (pe == 0 && (env_flag("VERSION") || env_flag("INFO") || s.debug)) {
@@ -896,6 +899,7 @@ void shmem_finalize(void)
     small_local_release();
     amo_release();
     signal_release();
+    lock_release();
     if (s.collect_lens) (void)hipHostFree(s.collect_lens);
     s.collect_lens = nullptr;
     if (s.stripes) (void)hipFree(s.stripes);

@@ -252,6 +252,10 @@ void small_local_release();
 void amo_release();
 // frees the waits' pinned snapshot buffer and put-with-signal's ticket word (signal.cpp)
 void signal_release();
+// the locks' pinned result record and device table of the PEs' heap bases (lock.cpp): built
+// at shmem_init, refilled when the device heap is created or mapped, freed by shmem_finalize
+void lock_table_build();
+void lock_release();
 void team_word_put(int which, int world_pe, uint64_t v);   // node shm (p2p.cpp)
 uint64_t team_word_get(int which, int world_pe);
 // p2p signalling mode (p2p.cpp): stream-ordered device signals on the registered shm

@@ -135,6 +135,22 @@ _RUNTIME = {
     "shmem_signal_wait_until": (_c.c_uint64, [_c.c_void_p, _c.c_int, _c.c_uint64]),
     "shmem_wait": (None, [_c.c_void_p, _c.c_long]),
     "shmem_wait_until": (None, [_c.c_void_p, _c.c_int, _c.c_long]),
+    # distributed locks: the three names, the generic entries, the check and message functions and the
+    # kernel's C ABI (lock.cpp, lock_checks.cpp, lock.hip)
+    "shmem_set_lock": (None, [_c.c_void_p]),
+    "shmem_clear_lock": (None, [_c.c_void_p]),
+    "shmem_test_lock": (_c.c_int, [_c.c_void_p]),
+    "sos_api_set_lock": (None, [_c.c_void_p, _c.c_char_p]),
+    "sos_api_clear_lock": (None, [_c.c_void_p, _c.c_char_p]),
+    "sos_api_test_lock": (_c.c_int, [_c.c_void_p, _c.c_char_p]),
+    "sos_lock_check": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_char_p, _c.c_size_t]),
+    "sos_lock_expiry_message": (None, [_c.c_char_p, _c.c_void_p, _c.c_int, _c.c_uint32, _c.c_double, _c.c_char_p,
+                                       _c.c_size_t]),
+    "sos_lock_corrupt_message": (None, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_char_p, _c.c_size_t]),
+    "sosx_lock_step": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_int,
+                                  _c.c_void_p, _c.c_void_p]),
+    "sosx_lock_table": (_c.c_void_p, [_c.POINTER(_c.c_int)]),
+    "sosx_lock_stats": (None, [_c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
     "sosx_prof_enable": (None, [_c.c_int]),
     "sosx_prof_get": (None, [_c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                              _c.POINTER(_c.c_long), _c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
