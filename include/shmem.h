@@ -62,6 +62,15 @@ typedef struct {
 } shmem_team_config_t;
 #define SHMEM_TEAM_NUM_CONTEXTS (1L << 0)
 
+/* contexts (mpp/shmem-def.h.in:80-90): the same opaque handle type and option values as SOS */
+typedef struct shmem_impl_ctx_t {
+    int dummy;
+} * shmem_ctx_t;
+#define SHMEM_CTX_PRIVATE    (1l << 0)
+#define SHMEM_CTX_SERIALIZED (1l << 1)
+#define SHMEM_CTX_NOSTORE    (1l << 2)
+#define SHMEM_CTX_INVALID NULL
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -69,6 +78,7 @@ extern "C" {
 extern shmem_team_t SHMEM_TEAM_WORLD;
 extern shmem_team_t SHMEM_TEAM_SHARED;
 #define SHMEM_TEAM_INVALID NULL
+extern shmem_ctx_t SHMEM_CTX_DEFAULT;
 
 /* ---- library setup, exit and query (src/init_c.c, src/query_c.c) ---------- */
 SHMEM_FUNCTION_ATTRIBUTES void shmem_init(void);
@@ -163,5 +173,9 @@ int pshmem_broadcastmem(shmem_team_t team, void *dest, const void *source, size_
 
 /* ---- distributed locks: set_lock, clear_lock, test_lock ---------------------- */
 #include "shmem_lock.h"
+
+/* ---- communication contexts: shmem_ctx_* management and the ctx form of every put, get,
+ * atomic and put-with-signal (generated); redefines the generics to take a leading ctx --- */
+#include "shmem_ctx.h"
 
 #endif /* SHMEM_H */

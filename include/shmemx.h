@@ -88,5 +88,6 @@ SHMEM_FUNCTION_ATTRIBUTES int sosx_loopback_collect(int P, void *const *srcs, vo
 /* ---- team prefix sums (generated: sos_amd/csrc/gen_bindings.py) ------------- */
 #include "shmemx_scans.h"
 #include "shmemx_rma.h"
+#include "shmemx_ctx.h"
 
 #endif /* SHMEMX_H */

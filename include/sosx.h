@@ -263,11 +263,16 @@ int sosx_amo(int op, void *target, uint64_t value, uint64_t cond, void *fetch, s
  * sig_addr, an unknown sig_op). */
 int sosx_put_signal(void *target, const void *source, size_t nbytes, uint64_t *sig_addr, uint64_t signal,
                     int sig_op, void *stream);
+/* The same launch counting its workgroups' arrivals on `ticket`: a zeroed 4-byte device word
+ * the caller owns, so that launches on different streams need not be serial (each
+ * communication context has one); NULL: the shared word of sosx_put_signal. */
+int sosx_put_signal_on(void *target, const void *source, size_t nbytes, uint64_t *sig_addr, uint64_t signal,
+                       int sig_op, unsigned *ticket, void *stream);
 /* The split that call would use (sos_amd/csrc/putsignal_plan.h): out = access width,
  * unaligned loads, head bytes, body accesses, tail bytes, tiles, workgroups, the most
  * workgroups any call uses.  Host only. */
 int sosx_put_signal_plan(uintptr_t target, uintptr_t source, size_t nbytes, long long out[8]);
-/* The ticket word (device memory; NULL before the first launch) and its release
+/* The shared ticket word (device memory; NULL before the first launch) and its release
  * (shmem_finalize calls it).  Introspection for tests. */
 void *sosx_put_signal_ticket(void);
 void sosx_put_signal_release(void);
@@ -385,6 +390,9 @@ void sosx_acquire_stats(long *acquires, long *peer_reads, long *unacquired, unsi
 /* Of those acquires, the stream-wide acquire kernels the p2p transport enqueued (the rest
  * ran in the workgroups of the small consuming launches themselves).  For tests. */
 long sosx_acquire_kernels(void);
+/* How many pool streams created communication contexts share: SHMEMX_CTX_STREAMS (1..31)
+ * as read at the first shmem_ctx_create, 3 before that and by default. */
+int sosx_ctx_streams(void);
 
 /* One acquire kernel on `stream`: 64 workgroups, each running a system-scope acquire
  * (buffer_inv sc0 sc1: this CU's L1 and its XCD's L2 drop lines other agents may have

@@ -8,7 +8,8 @@
 //
 //  * a target a kernel can reach -- any device-heap word, and for pe == my_pe the host
 //    heap or a registered data segment (device_view) -- gets one launch of sosx_amo
-//    (amo.hip) on the library stream: one system-scope read-modify-write;
+//    (amo.hip) on the stream of the call's context (SHMEM_CTX_DEFAULT's, the library
+//    stream, for the plain forms): one system-scope read-modify-write;
 //  * a target in this PE's own pageable memory (static data under SHMEMX_REGISTER_DATA=0)
 //    is memory only this process can address: the stream is completed, then the host does
 //    the operation with the compiler's __atomic builtins;
@@ -80,11 +81,12 @@ namespace {
 
 constexpr unsigned kRingSlots = 64;  // nbi results on their way to pageable memory
 
+// The ring of nbi results is the context's (Ctx::amo_ring): a fetching nbi atomic on
+// context A is filled by A's quiet.  The blocking forms' word is shared: they complete
+// their stream before they return, and the library is not thread-multiple.
 struct AmoState {
     uint64_t *result = nullptr;      // pinned host word: a blocking form's old value
     uint64_t *result_dev = nullptr;  // its device view
-    uint64_t *ring = nullptr;        // device slots
-    unsigned ring_used = 0;
 };
 
 AmoState &amo()
@@ -115,12 +117,15 @@ void sosrt::amo_release()
 {
     AmoState &a = amo();
     if (a.result) (void)hipHostFree(a.result);
-    if (a.ring) (void)hipFree(a.ring);
     a = AmoState();
+    Ctx &d = st().def_ctx;
+    if (d.amo_ring) (void)hipFree(d.amo_ring);
+    d.amo_ring = nullptr;
+    d.amo_ring_used = 0;
 }
 
-extern "C" void sos_api_amo(int op, void *target, const void *value, const void *cond, void *fetch_out,
-                            int want_old, size_t type_size, int is_float, int pe, int nbi, const char *fn)
+void sosrt::amo_on(Ctx &cx, int op, void *target, const void *value, const void *cond, void *fetch_out, int want_old,
+                   size_t type_size, int is_float, int pe, int nbi, const char *fn)
 {
     State &s = st();
     {
@@ -133,6 +138,7 @@ extern "C" void sos_api_amo(int op, void *target, const void *value, const void 
     if (op < SOSX_AMO_SET || op > SOSX_AMO_XOR ||
         (is_float && op != SOSX_AMO_SET && op != SOSX_AMO_FETCH && op != SOSX_AMO_SWAP))
         raise_error("%s: atomic operation %d is not defined on this type", fn, op);
+    ++cx.enqueued;
     const size_t ts = type_size;
     uint64_t v = 0, c = 0;
     if (value) memcpy(&v, value, ts);
@@ -143,7 +149,7 @@ extern "C" void sos_api_amo(int op, void *target, const void *value, const void 
     if (!tdev) {
         // this PE's own pageable memory (the checks let only pe == my_pe come here): after
         // what the stream still has queued, the host does it
-        hip_check(sync_system(s.stream), fn);
+        hip_check(sync_system(cx), fn);
         const uint64_t old = ts == 4 ? host_rmw<uint32_t>(op, (uint32_t *)t, (uint32_t)v, (uint32_t)c)
                                      : host_rmw<uint64_t>(op, (uint64_t *)t, v, c);
         if (want_old) memcpy(fetch_out, &old, ts);
@@ -151,36 +157,50 @@ extern "C" void sos_api_amo(int op, void *target, const void *value, const void 
     }
     AmoState &a = amo();
     if (!want_old) {
-        const int rc = sosx_amo(op, tdev, v, c, nullptr, ts, is_float, s.stream);
+        const int rc = sosx_amo(op, tdev, v, c, nullptr, ts, is_float, cx.stream);
         if (rc != SOSX_OK) raise_error("%s: atomic launch failed (%d)", fn, rc);
         return;
     }
-    before_peer_read(pe, fn);
+    before_peer_read(cx, pe, fn);
     if (!nbi) {
         if (!a.result) {
             hip_check(hipHostMalloc((void **)&a.result, sizeof(uint64_t), hipHostMallocDefault), "hipHostMalloc(amo)");
             hip_check(hipHostGetDevicePointer((void **)&a.result_dev, a.result, 0), "hipHostGetDevicePointer(amo)");
         }
-        const int rc = sosx_amo(op, tdev, v, c, a.result_dev, ts, is_float, s.stream);
+        const int rc = sosx_amo(op, tdev, v, c, a.result_dev, ts, is_float, cx.stream);
         if (rc != SOSX_OK) raise_error("%s: atomic launch failed (%d)", fn, rc);
-        hip_check(sync_system(s.stream), fn);
+        hip_check(sync_system(cx), fn);
         memcpy(fetch_out, a.result, ts);
         return;
     }
     if (char *fdev = device_view(fetch_out, ts)) {
-        const int rc = sosx_amo(op, tdev, v, c, fdev, ts, is_float, s.stream);
+        const int rc = sosx_amo(op, tdev, v, c, fdev, ts, is_float, cx.stream);
         if (rc != SOSX_OK) raise_error("%s: atomic launch failed (%d)", fn, rc);
         return;
     }
     // pageable `fetch`: a ring slot, then a copy on the same stream
-    if (!a.ring) hip_check(hipMalloc((void **)&a.ring, kRingSlots * sizeof(uint64_t)), "hipMalloc(amo ring)");
-    if (a.ring_used == kRingSlots) {
-        hip_check(sync_system(s.stream), fn);
-        a.ring_used = 0;
+    if (!cx.amo_ring) hip_check(hipMalloc((void **)&cx.amo_ring, kRingSlots * sizeof(uint64_t)), "hipMalloc(amo ring)");
+    if (cx.amo_ring_used == kRingSlots) {
+        hip_check(sync_system(cx), fn);
+        cx.amo_ring_used = 0;
     }
-    uint64_t *slot = a.ring + a.ring_used++;
-    const int rc = sosx_amo(op, tdev, v, c, slot, ts, is_float, s.stream);
+    uint64_t *slot = cx.amo_ring + cx.amo_ring_used++;
+    const int rc = sosx_amo(op, tdev, v, c, slot, ts, is_float, cx.stream);
     if (rc != SOSX_OK) raise_error("%s: atomic launch failed (%d)", fn, rc);
-    hip_check(release_system(s.stream), fn);  // the copy engine reads HBM
-    hip_check(hipMemcpyAsync(fetch_out, slot, ts, hipMemcpyDeviceToHost, s.stream), fn);
+    hip_check(release_system(cx), fn);  // the copy engine reads HBM
+    hip_check(hipMemcpyAsync(fetch_out, slot, ts, hipMemcpyDeviceToHost, cx.stream), fn);
+}
+
+extern "C" void sos_api_amo(int op, void *target, const void *value, const void *cond, void *fetch_out,
+                            int want_old, size_t type_size, int is_float, int pe, int nbi, const char *fn)
+{
+    amo_on(default_ctx(), op, target, value, cond, fetch_out, want_old, type_size, is_float, pe, nbi, fn);
+}
+
+extern "C" void sos_api_ctx_amo(shmem_ctx_t ctx, int op, void *target, const void *value, const void *cond,
+                                void *fetch_out, int want_old, size_t type_size, int is_float, int pe, int nbi,
+                                const char *fn)
+{
+    Ctx &cx = ctx_checked(ctx, &pe, fn);
+    amo_on(cx, op, target, value, cond, fetch_out, want_old, type_size, is_float, pe, nbi, fn);
 }

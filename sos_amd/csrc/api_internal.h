@@ -202,6 +202,67 @@ void sos_lock_expiry_message(const char *fn, const void *lock, int awaited, uint
                              size_t msg_len);
 void sos_lock_corrupt_message(const void *lock, int value, int n_pes, char *msg, size_t msg_len);
 
+// ---- communication contexts (ctx.cpp; the checks: ctx_checks.cpp) ------------------------
+// The public shmem_ctx_* names are ctx_gen.cpp's, in a library of their own
+// (libsos_amd_ctx.so) over these entries: libsos_amd.so exports no shmem_ctx_ name.
+// The ctx twin of every entry above that has one in SOS: the handle is checked, `pe` is
+// read as an index of the context's team, and the operation runs on the context's stream.
+int sos_api_ctx_create(long options, shmem_ctx_t *ctx);
+int sos_api_team_create_ctx(shmem_team_t team, long options, shmem_ctx_t *ctx);
+int sos_api_ctx_get_team(shmem_ctx_t ctx, shmem_team_t *team);
+void sos_api_ctx_destroy(shmem_ctx_t ctx);
+void sos_api_ctx_quiet(shmem_ctx_t ctx);
+void sos_api_ctx_fence(shmem_ctx_t ctx);
+void sos_api_ctx_put(shmem_ctx_t ctx, void *dest, const void *source, size_t nelems, size_t type_size, int pe,
+                     int nbi, const char *fn);
+void sos_api_ctx_get(shmem_ctx_t ctx, void *dest, const void *source, size_t nelems, size_t type_size, int pe,
+                     int nbi, const char *fn);
+void sos_api_ctx_iput(shmem_ctx_t ctx, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      size_t type_size, int pe, const char *fn);
+void sos_api_ctx_iget(shmem_ctx_t ctx, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      size_t type_size, int pe, const char *fn);
+void sos_api_ctx_ibput(shmem_ctx_t ctx, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize,
+                       size_t nblocks, size_t type_size, int pe, const char *fn);
+void sos_api_ctx_ibget(shmem_ctx_t ctx, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize,
+                       size_t nblocks, size_t type_size, int pe, const char *fn);
+void sos_api_ctx_p(shmem_ctx_t ctx, void *addr, const void *value, size_t type_size, int pe, const char *fn);
+void sos_api_ctx_g(shmem_ctx_t ctx, void *value, const void *addr, size_t type_size, int pe, const char *fn);
+void sos_api_ctx_amo(shmem_ctx_t ctx, int op, void *target, const void *value, const void *cond, void *fetch_out,
+                     int want_old, size_t type_size, int is_float, int pe, int nbi, const char *fn);
+void sos_api_ctx_put_signal(shmem_ctx_t ctx, void *dest, const void *source, size_t nelems, size_t type_size,
+                            uint64_t *sig_addr, uint64_t signal, int sig_op, int pe, int nbi, const char *fn);
+void sos_api_ctx_signal_op(shmem_ctx_t ctx, uint64_t *sig_addr, uint64_t signal, int sig_op, int pe, const char *fn);
+
+// The handle check, the option check, the team-index translation and the stream-pool
+// assignment as plain functions of data (ctx_checks.cpp has no HIP include): 0, or a code
+// with its message.  A handle is looked up in the table of live contexts, never
+// dereferenced: SHMEM_CTX_INVALID, a destroyed context and any other pointer are refused.
+enum { SOS_CTX_OK = 0,
+       SOS_CTX_BAD_PE = SOS_RMA_BAD_PE,  // the index is outside the context's team
+       SOS_CTX_INVALID = 14,       // SHMEM_CTX_INVALID
+       SOS_CTX_DESTROYED = 15,     // a handle shmem_ctx_destroy (or a team's / the library's teardown) freed
+       SOS_CTX_UNKNOWN = 16,       // no context this library created
+       SOS_CTX_BAD_OPTIONS = 17 }; // bits outside SHMEM_CTX_PRIVATE | _SERIALIZED | _NOSTORE
+typedef struct {
+    const void *handle;
+    int start, stride, size;  // the context's team in world PEs
+} sos_ctx_entry;
+typedef struct {
+    int nlive;
+    const sos_ctx_entry *live;  // SHMEM_CTX_DEFAULT's entry included
+    int ndead;
+    const void *const *dead;    // handles destroyed and not reused since
+} sos_ctx_table;
+// *index: the entry of `handle` in live; *pe (or NULL: a call without one) goes from a team
+// index to a world PE, refused with put / get's bad-PE message outside [0, size).
+int sos_ctx_check(const sos_ctx_table *table, const void *handle, int *pe, int *index, char *msg, size_t msg_len);
+int sos_ctx_options_check(long options, char *msg, size_t msg_len);
+// SHMEMX_CTX_STREAMS as the environment gives it (NULL: unset): 1..31, default 3; -1 with a
+// message for anything else.
+int sos_ctx_pool_size(const char *env_value, char *msg, size_t msg_len);
+// The pool slot of the context created after `created` others: round-robin.
+int sos_ctx_stream_slot(unsigned long created, int pool_size);
+
 #ifdef __cplusplus
 }
 
@@ -217,9 +278,16 @@ const sos_rma_region *rma_find_region(const sos_rma_layout *l, uintptr_t p);
 const char *rma_region_name(int kind);
 // the remote side's address on this PE
 char *translate(const void *remote, int pe);
-// Before a launch or copy that reads peer `pe`'s heap: the acquire a wait since the last
-// one left owed, and the read counted.
-void before_peer_read(int pe, const char *fn);
+struct Ctx;
+// Before a launch or copy on context `c` that reads peer `pe`'s heap: the acquire a wait
+// since the context's last one left owed, on its stream, and the read counted.
+void before_peer_read(Ctx &c, int pe, const char *fn);
+// The entries behind sos_api_put / sos_api_amo and their ctx twins, for callers that
+// already hold the context and a world PE (put-with-signal's composed form, the signal ops).
+void rma_put_on(Ctx &c, void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi,
+                const char *fn);
+void amo_on(Ctx &c, int op, void *target, const void *value, const void *cond, void *fetch_out, int want_old,
+            size_t type_size, int is_float, int pe, int nbi, const char *fn);
 // The address at which a kernel on this PE's GPU reaches the `bytes` bytes at p, or null
 // where it cannot (rma.cpp).
 char *device_view(const void *p, size_t bytes);

@@ -47,6 +47,14 @@ makes their min/max compare signed -- and writes:
   sos_amd/csrc/signal_gen.cpp     their definitions (src/data_c.c4:684-784,
                                   src/synchronization_c.c4) over signal.cpp
 
+  include/shmem_ctx.h             the communication contexts: shmem_ctx_create / destroy / quiet / fence,
+                                  shmem_team_create_ctx, shmem_ctx_get_team and the shmem_ctx_ twin of
+                                  every put, get, atomic and put with signal; redefines the generics to
+                                  take a leading shmem_ctx_t (mpp/shmem_c_func.h4, mpp/shmem.h4)
+  include/shmemx_ctx.h            shmemx_ctx_<T>_{ibput,ibget}, shmemx_ctx_ib{put,get}<N>,
+                                  shmemx_ctx_signal_add / _set
+  sos_amd/csrc/ctx_gen.cpp        their definitions over the sos_api_ctx_* entries
+
 The library's Makefile compiles every *.cpp of the directory, so a new generated source
 needs no entry there.
 
@@ -519,8 +527,8 @@ def rma_header(which):
         out += [" * SOS's one-sided put / get family on the symmetric heaps: the typed forms",
                 " * shmem_<T>_{put,get,put_nbi,get_nbi,p,g,iput,iget} over the 24 RMA types, the sized",
                 " * forms for 8..128 bits, putmem / getmem, shmem_ptr, the C11 generic selectors and the",
-                " * C++ overloads (mpp/shmem_c_func.h4:46-241).  There are no contexts: the shmem_ctx_*",
-                " * forms are not provided.  Included from shmem.h. */"]
+                " * C++ overloads (mpp/shmem_c_func.h4:46-241).  The shmem_ctx_* forms are in shmem_ctx.h.",
+                " * Included from shmem.h. */"]
     else:
         out += [" * SOS's block-strided extension shmemx_<T>_{ibput,ibget} and shmemx_{ibput,ibget}<N>",
                 " * (mpp/shmemx_c_func.h4:32-71): nblocks blocks of bsize elements, tst / sst elements",
@@ -559,7 +567,7 @@ def rma_source():
 
 # ---- atomic memory operations (SHMEM_DECLARE_FOR_AMO / _EXTENDED_AMO / _BITWISE_AMO:
 # mpp/shmem_c_func.h4:243-404, :575-639; bindings/shmem_bind_c.m4:43-69; src/atomic_c.c4,
-# src/atomic_nbi_c.c4).  There are no contexts: the shmem_ctx_* forms are not provided.
+# src/atomic_nbi_c.c4).  The shmem_ctx_* forms: ctx_entries below.
 AMO = [("int", "int"), ("long", "long"), ("longlong", "long long"), ("uint", "unsigned int"),
        ("ulong", "unsigned long"), ("ulonglong", "unsigned long long"), ("int32", "int32_t"),
        ("int64", "int64_t"), ("uint32", "uint32_t"), ("uint64", "uint64_t"), ("size", "size_t"),
@@ -670,8 +678,8 @@ def amo_header():
            " * :575-639): compare_swap, fetch_inc, inc, fetch_add, add over the 12 AMO types; swap,",
            " * fetch, set over those and float, double; and, or, xor and their fetching forms over the",
            " * 7 bitwise types; the deprecated pre-1.4 names; the nbi fetching forms; the C11 generic",
-           " * selectors and the C++ overloads.  There are no contexts: the shmem_ctx_* forms are not",
-           " * provided.  Included from shmem.h. */",
+           " * selectors and the C++ overloads.  The shmem_ctx_* forms are in shmem_ctx.h.  Included from",
+           " * shmem.h. */",
            "#ifndef SHMEM_AMO_H", "#define SHMEM_AMO_H", "",
            "#ifndef SHMEM_ATTRIBUTE_DEPRECATED",
            "#define SHMEM_ATTRIBUTE_DEPRECATED __attribute__((deprecated))", "#endif", "",
@@ -702,8 +710,8 @@ def amo_source():
 
 # ---- put with signal, signal operations, point-to-point synchronisation
 # (mpp/shmem_c_func.h4:91-127, :473-542, :705; mpp/shmemx_c_func.h4:98-100;
-# bindings/shmem_bind_c.m4:71-91; src/data_c.c4:684-784, src/synchronization_c.c4).  There are
-# no contexts: the shmem_ctx_* forms are not provided.
+# bindings/shmem_bind_c.m4:71-91; src/data_c.c4:684-784, src/synchronization_c.c4).  The
+# shmem_ctx_* forms of put with signal: ctx_entries below.
 WAIT = [("short", "short"), ("int", "int"), ("long", "long"), ("longlong", "long long")]
 SYNC = WAIT + [("ushort", "unsigned short"), ("uint", "unsigned int"), ("ulong", "unsigned long"),
                ("ulonglong", "unsigned long long"), ("int32", "int32_t"), ("int64", "int64_t"),
@@ -867,7 +875,7 @@ def signal_header(sec):
                 " * 24 RMA types, the sized forms for 8..128 bits, putmem_signal[_nbi], shmem_signal_fetch",
                 " * and SOS's extensions shmemx_signal_add / shmemx_signal_set (mpp/shmem_c_func.h4:91-127,",
                 " * :705; mpp/shmemx_c_func.h4:98-100), with the C11 generic selectors and the C++ overloads.",
-                " * There are no contexts: the shmem_ctx_* forms are not provided.  Included from shmem.h. */"]
+                " * The shmem_ctx_* forms are in shmem_ctx.h.  Included from shmem.h. */"]
     else:
         out += [" * SOS's point-to-point synchronisation (mpp/shmem_c_func.h4:473-542): shmem_<T>_wait_until",
                 " * and shmem_<T>_test with their _all / _any / _some and _vector forms over the 14 SYNC",
@@ -918,6 +926,286 @@ def signal_source():
     return "\n".join(out)
 
 
+# ---- communication contexts: the ctx twin of every put, get, atomic and put-with-signal
+# (mpp/shmem_c_func.h4:60-406, :547-658; mpp/shmemx_c_func.h4:32-101; the shmem_ctx_* stamping
+# of src/data_c.c4:820-880).  A twin is its plain form with "ctx_" after the prefix, a leading
+# shmem_ctx_t and the sos_api_ctx_* entry.  The deprecated atomics, the waits and tests,
+# shmem_signal_fetch, shmem_ptr and the locks have none.
+#
+# The 575 twins are not written out: the headers and ctx_gen.cpp hold each FORM once, as a
+# macro over (name part, C type) -- or (bits, bytes) for the sized forms -- and stamp it over
+# X-macro type tables, as SOS stamps its own out of m4 tables.  ctx_entries() is the same
+# expansion done here, for the name list, the Python mirrors and the tests, which compare it
+# with what the preprocessor makes of the headers.
+#
+# The public names live in a library of their own, sos_amd/libsos_amd_ctx.so (ctx_gen.cpp
+# alone), over the sos_api_ctx_* entries of libsos_amd.so: that library's export list is
+# pinned to hold no shmem_ctx_ name.
+CTX_MANAGEMENT = [
+    ("shmem_ctx_create", "int", "long options, shmem_ctx_t *ctx", "return sos_api_ctx_create(options, ctx);"),
+    ("shmem_ctx_destroy", "void", "shmem_ctx_t ctx", "sos_api_ctx_destroy(ctx);"),
+    ("shmem_ctx_quiet", "void", "shmem_ctx_t ctx", "sos_api_ctx_quiet(ctx);"),
+    ("shmem_ctx_fence", "void", "shmem_ctx_t ctx", "sos_api_ctx_fence(ctx);"),
+    ("shmem_team_create_ctx", "int", "shmem_team_t team, long options, shmem_ctx_t *ctx",
+     "return sos_api_team_create_ctx(team, options, ctx);"),
+    ("shmem_ctx_get_team", "int", "shmem_ctx_t ctx, shmem_team_t *team", "return sos_api_ctx_get_team(ctx, team);")]
+# X-macro tables: name -> rows (name part, second column)
+CTX_TABLES = {
+    "RMA": RMA, "SIZES": [(str(b), str(b // 8)) for b in RMA_SIZES],
+    "SIZES_MEM": [(str(b), str(b // 8)) for b in RMA_SIZES] + [("mem", "1")],
+    "AMO": AMO, "EXTENDED_AMO": EXTENDED_AMO, "BITWISE_AMO": BITWISE_AMO}
+_CTX_SIZED = ("SIZES", "SIZES_MEM")   # their second column is SZ, the element's bytes; else T, its C type
+
+
+def ctx_forms():
+    """(header, family, table, return type, name before the type, name after it, parameters
+    after ctx, body) of every ctx FORM; T / SZ stand for the table's second column, fn for the
+    entry's own name."""
+    out = []
+    for table, ptr, size in (("RMA", "T", "sizeof(T)"), ("SIZES", "void", "SZ"), ("SIZES_MEM", "void", "SZ")):
+        typed = table == "RMA"
+        pre, mid = ("shmem_ctx_", "_") if typed else ("shmem_ctx_", "")
+        xpre = "shmemx_ctx_"
+        two = f"{ptr} *target, const {ptr} *source"
+        if table != "SIZES":
+            for kind in _RMA_CONTIG:
+                api, _, nbi = kind.partition("_")
+                out.append(("shmem", "rma", table, "void", pre + ("" if typed else api), (mid + kind) if typed else
+                            ("_nbi" if nbi else ""), f"{two}, size_t nelems, int pe",
+                            f"sos_api_ctx_{api}(ctx, target, source, nelems, {size}, pe, {1 if nbi else 0}, fn);"))
+            for nbi, sfx in ((0, ""), (1, "_nbi")):
+                out.append(("shmem", "signal", table, "void", pre + ("" if typed else "put"),
+                            (mid + "put_signal" + sfx) if typed else ("_signal" + sfx), f"{two}, {_PUT_SIGNAL_ARGS}",
+                            f"sos_api_ctx_put_signal(ctx, target, source, nelems, {size}, sig_addr, signal, sig_op, "
+                            f"pe, {nbi}, fn);"))
+        if typed:
+            out.append(("shmem", "rma", table, "void", pre, "_p", "T *addr, T value, int pe",
+                        "sos_api_ctx_p(ctx, addr, &value, sizeof(T), pe, fn);"))
+            out.append(("shmem", "rma", table, "T", pre, "_g", "const T *addr, int pe",
+                        "T tmp; sos_api_ctx_g(ctx, &tmp, addr, sizeof(T), pe, fn); return tmp;"))
+        if table != "SIZES_MEM":
+            for kind in _RMA_STRIDED:
+                out.append(("shmem", "rma", table, "void", pre + ("" if typed else kind), (mid + kind) if typed else "",
+                            f"{two}, {_STRIDED_ARGS}", f"sos_api_ctx_{kind}(ctx, target, source, tst, sst, len, {size}, pe, fn);"))
+            for kind in _RMA_BLOCK:
+                out.append(("shmemx", "rma", table, "void", xpre + ("" if typed else kind), (mid + kind) if typed else "",
+                            f"{two}, {_BLOCK_ARGS}",
+                            f"sos_api_ctx_{kind}(ctx, target, source, tst, sst, bsize, nblocks, {size}, pe, fn);"))
+    for form, (table, op, args, old, dep) in AMO_FORMS.items():
+        if dep:
+            continue
+        params, _ = _amo_params(form, "T")
+        value = "&value" if ("v" in args or "1" in args) else "NULL"
+        call = (f"sos_api_ctx_amo(ctx, SOSX_AMO_{op}, {'(void *)target' if op == 'FETCH' else 'target'}, {value}, "
+                f"{'&cond' if 'c' in args else 'NULL'}, {{'r': '&old', 'n': 'fetch', '': 'NULL'}}, {1 if old else 0}, "
+                f"sizeof(T), (T)0.5 != (T)0, pe, {1 if old == 'n' else 0}, fn);").replace(
+                    "{'r': '&old', 'n': 'fetch', '': 'NULL'}", {"r": "&old", "n": "fetch", "": "NULL"}[old])
+        body = ("T value = 1; " if "1" in args else "") + (f"T old; {call} return old;" if old == "r" else call)
+        out.append(("shmem", "amo", table, "T" if old == "r" else "void", "shmem_ctx_", "_" + form, params, body))
+    return out
+
+
+def _ctx_subst(text, second, sized):
+    import re
+    return re.sub(r"\bSZ\b" if sized else r"\bT\b", second, text)
+
+
+_CTX_SIGNAL_OPS = [(f"shmemx_ctx_signal_{op}", f"sos_api_ctx_signal_op(ctx, sig_addr, signal, SOSX_SIGNAL_{op.upper()}, pe, fn);")
+                   for op in ("add", "set")]
+_CTX_SIGNAL_OP_PARAMS = "uint64_t *sig_addr, uint64_t signal, int pe"
+
+
+def ctx_entries():
+    """(header, family, name, sig(prefix)) of every ctx twin: the forms expanded over their
+    tables, and the two signal operations."""
+    out = []
+    for hdr, family, table, ret, pre, suf, params, _ in ctx_forms():
+        sized = table in _CTX_SIZED
+        for first, second in CTX_TABLES[table]:
+            name = pre + first + suf
+            proto = (f"{_ctx_subst(ret, second, sized)} {{p}}{name}(shmem_ctx_t ctx, "
+                     f"{_ctx_subst(params, second, sized)})")
+            out.append((hdr, family, name, lambda p, proto=proto: proto.format(p=p)))
+    for name, _ in _CTX_SIGNAL_OPS:
+        proto = f"void {{p}}{name}(shmem_ctx_t ctx, {_CTX_SIGNAL_OP_PARAMS})"
+        out.append(("shmemx", "signal", name, lambda p, proto=proto: proto.format(p=p)))
+    return out
+
+
+def ctx_symbols():
+    """Every public context name: the six management calls and the twins."""
+    return [n for n, _, _, _ in CTX_MANAGEMENT] + [name for _, _, name, _ in ctx_entries()]
+
+
+def _ctx_macro(head, lines):
+    return [head + " \\"] + [f"    {ln} \\" for ln in lines[:-1]] + [f"    {lines[-1]}"]
+
+
+def _ctx_stamp(which, macro, item):
+    """One macro per table holding every form of header `which` -- item(form) is its line --
+    and the table's stamping of it."""
+    out = []
+    for table in CTX_TABLES:
+        forms = [f for f in ctx_forms() if f[0] == which and f[2] == table]
+        if forms:
+            second = "SZ" if table in _CTX_SIZED else "T"
+            out += _ctx_macro(f"#define {macro}_{table}(N, {second})", [item(f) for f in forms])
+            out += [f"SHMEM_CTX_FOR_{table}({macro}_{table})", f"#undef {macro}_{table}"]
+    return out
+
+
+def _ctx_name_tokens(pre, suf):
+    return f"{pre}##N{'##' + suf if suf else ''}"
+
+
+_CTX_C11_TABLES = {"RMA": GENERIC_RMA, "AMO": AMO_GENERIC_C11["AMO"], "EXTENDED_AMO": AMO_GENERIC_C11["EXTENDED_AMO"],
+                   "BITWISE_AMO": AMO_GENERIC_C11["BITWISE_AMO"]}
+_CTX_CXX_TABLES = {"RMA": GENERIC_RMA, "AMO": AMO_GENERIC_CXX["AMO"], "EXTENDED_AMO": AMO_GENERIC_CXX["EXTENDED_AMO"],
+                   "BITWISE_AMO": AMO_GENERIC_CXX["BITWISE_AMO"]}
+
+
+def _ctx_generic_list(which):
+    """(generic name, table, ctx prefix, plain prefix, suffix, C++ return, C++ parameters, C++
+    argument names, const ctx arms, const plain arms) of every generic of header `which`."""
+    out = []
+    if which == "shmem":
+        for kind in _RMA_CONTIG + _RMA_STRIDED:
+            params, args = _rma_generic_args(kind)
+            out.append((f"shmem_{kind}", "RMA", "shmem_ctx_", "shmem_", f"_{kind}", "void",
+                        f"T *target, const T *source, {params}", f"target, source, {args}", False, False))
+        out.append(("shmem_p", "RMA", "shmem_ctx_", "shmem_", "_p", "void", "T *addr, T value, int pe", "addr, value, pe",
+                    False, False))
+        out.append(("shmem_g", "RMA", "shmem_ctx_", "shmem_", "_g", "T", "const T *addr, int pe", "addr, pe", True, True))
+        for form, (table, op, args, old, dep) in AMO_FORMS.items():
+            if not dep:
+                params, names = _amo_params(form, "T")
+                # the blocking fetch selects on its const target; the nbi forms on `fetch`
+                out.append((f"shmem_{form}", table, "shmem_ctx_", "shmem_", f"_{form}", "T" if old == "r" else "void",
+                            params, names, op == "FETCH" and old != "n", op == "FETCH"))
+        for sfx in ("", "_nbi"):
+            out.append((f"shmem_put_signal{sfx}", "RMA", "shmem_ctx_", "shmem_", f"_put_signal{sfx}", "void",
+                        f"T *dest, const T *source, {_PUT_SIGNAL_ARGS}", f"dest, source, {_PUT_SIGNAL_NAMES}", False, False))
+    else:
+        for kind in _RMA_BLOCK:
+            params, args = _rma_generic_args(kind)
+            out.append((f"shmemx_{kind}", "RMA", "shmemx_ctx_", "shmemx_", f"_{kind}", "void",
+                        f"T *target, const T *source, {params}", f"target, source, {args}", False, False))
+    return out
+
+
+def _ctx_generics(which):
+    gens = _ctx_generic_list(which)
+    out = ["#if defined(__cplusplus)"]
+    if which == "shmem":
+        for table, rows in _CTX_CXX_TABLES.items():
+            out.append(f"#define SHMEM_CTX_FOR_CXX_{table}(X) " + " ".join(f"X({st}, {ct})" for st, ct in rows))
+    for table in _CTX_CXX_TABLES:
+        lines = [f"static inline {ret} {g}(shmem_ctx_t ctx, {params}) {{ {'return ' if ret != 'void' else ''}"
+                 f"{cp}##N##{s}(ctx, {names}); }}" for g, t, cp, pp, s, ret, params, names, _, _ in gens if t == table]
+        if lines:
+            out += _ctx_macro(f"#define SHMEM_CTX_CXX_{table}(N, T)", lines)
+            out += [f"SHMEM_CTX_FOR_CXX_{table}(SHMEM_CTX_CXX_{table})", f"#undef SHMEM_CTX_CXX_{table}"]
+    if which == "shmemx":
+        for op in ("add", "set"):
+            out.append(f"static inline void shmemx_signal_{op}(shmem_ctx_t ctx, {_CTX_SIGNAL_OP_PARAMS}) "
+                       f"{{ shmemx_ctx_signal_{op}(ctx, sig_addr, signal, pe); }}")
+    out.append("#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L")
+    if which == "shmem":
+        out += c11_prelude()
+        out += ["#ifndef SHMEM_C11_ARG0", "#define SHMEM_C11_ARG0(...) SHMEM_C11_ARG0_HELPER(__VA_ARGS__, sentinel)",
+                "#define SHMEM_C11_ARG0_HELPER(first, ...) first", "#endif",
+                "#define SHMEM_C11_TYPE_EVAL_PTR_OR_SCALAR(arg) (arg)+0",
+                "/* matches no call: selecting it is a compile-time error */",
+                "static inline void shmem_ctx_c11_generic_selection_failed(void) { }",
+                "/* the arms of a selector over one type table: <type>*: <p><name part><s> (and the const",
+                " * pointers for the forms that read their target) */"]
+        for table, rows in _CTX_C11_TABLES.items():
+            arms = ", ".join(f"{ct}*: p##{st}##s" for st, ct in rows)
+            out.append(f"#define SHMEM_CTX_ARMS_{table}(p, s) {arms}")
+            out.append(f"#define SHMEM_CTX_CARMS_{table}(p, s) SHMEM_CTX_ARMS_{table}(p, s), "
+                       + ", ".join(f"const {ct}*: p##{st}##s" for st, ct in rows))
+        out += ["/* a selector that takes an optional leading context: the first argument chooses between the",
+                " * ctx forms (arms CA over prefix cp), selected by the second argument, and the plain forms",
+                " * (arms PA over prefix pp) */"]
+        out += _ctx_macro("#define SHMEM_CTX_SELECT(CA, PA, cp, pp, s, ...)",
+                          ["_Generic(SHMEM_C11_TYPE_EVAL_PTR(SHMEM_C11_ARG0(__VA_ARGS__)),",
+                           "    shmem_ctx_t: _Generic(SHMEM_C11_TYPE_EVAL_PTR_OR_SCALAR(SHMEM_C11_ARG1(__VA_ARGS__)),",
+                           "        CA(cp, s), default: shmem_ctx_c11_generic_selection_failed),",
+                           "    PA(pp, s))(__VA_ARGS__)"])
+    for g, table, cp, pp, s, _, _, _, cconst, pconst in gens:
+        ca = f"SHMEM_CTX_{'CARMS' if cconst else 'ARMS'}_{table}"
+        pa = f"SHMEM_CTX_{'CARMS' if pconst else 'ARMS'}_{table}"
+        out += [f"#undef {g}", f"#define {g}(...) SHMEM_CTX_SELECT({ca}, {pa}, {cp}, {pp}, {s}, __VA_ARGS__)"]
+    if which == "shmemx":
+        for op in ("add", "set"):
+            out += [f"#define shmemx_signal_{op}(...) _Generic(SHMEM_C11_TYPE_EVAL_PTR(SHMEM_C11_ARG0(__VA_ARGS__)), \\",
+                    f"    shmem_ctx_t: shmemx_ctx_signal_{op}, uint64_t*: shmemx_signal_{op})(__VA_ARGS__)"]
+    out.append("#endif")
+    return out
+
+
+def ctx_header(which):
+    fname = "shmem_ctx.h" if which == "shmem" else "shmemx_ctx.h"
+    guard = fname.upper().replace(".", "_")
+    out = [f"/* {fname} -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", " *"]
+    if which == "shmem":
+        out += [" * SOS's communication contexts (mpp/shmem_c_func.h4:60-406, :547-658): shmem_ctx_create /",
+                " * destroy / quiet / fence, shmem_team_create_ctx, shmem_ctx_get_team, and the shmem_ctx_ twin",
+                " * of every put, get, p, g, iput, iget, non-deprecated atomic and put with signal.  Each FORM",
+                " * is declared once, as a macro over (name part, C type) -- (bits, bytes) for the sized forms",
+                " * -- stamped over the type tables below; `cc -E` shows the prototypes written out.  The C++",
+                " * overloads gain a form with a leading shmem_ctx_t, and the C11 selectors are redefined to",
+                " * take one: shmem_put(ctx, dest, source, nelems, pe).  The symbols are in libsos_amd_ctx.so:",
+                " * link -lsos_amd_ctx -lsos_amd.  Included last from shmem.h. */"]
+    else:
+        out += [" * The context twins of SOS's extensions (mpp/shmemx_c_func.h4:32-101): shmemx_ctx_<T>_{ibput,",
+                " * ibget}, shmemx_ctx_ib{put,get}<N>, shmemx_ctx_signal_add / _set, with the generics taking a",
+                " * leading shmem_ctx_t; declared as shmem_ctx.h declares its own.  Included last from shmemx.h. */"]
+    out += [f"#ifndef {guard}", f"#define {guard}", ""]
+    if which == "shmem":
+        out += ["/* the type tables (bindings/shmem_bind_c.m4): X(name part, C type); sizes: X(bits, bytes) */"]
+        for table, rows in CTX_TABLES.items():
+            out.append(f"#define SHMEM_CTX_FOR_{table}(X) " + " ".join(f"X({a}, {b})" for a, b in rows))
+        out += ["/* one entry point: the shmem_ name and its pshmem_ twin (the profiling interface) */",
+                "#define SHMEM_CTX_DECL(ret, name, params) SHMEM_FUNCTION_ATTRIBUTES ret name params; ret p##name params;"]
+    out += ["", "#ifdef __cplusplus", 'extern "C" {', "#endif", ""]
+    if which == "shmem":
+        for name, ret, params, _ in CTX_MANAGEMENT:
+            out.append(f"SHMEM_CTX_DECL({ret}, {name}, ({params}))")
+    else:
+        for name, _ in _CTX_SIGNAL_OPS:
+            out.append(f"SHMEM_CTX_DECL(void, {name}, (shmem_ctx_t ctx, {_CTX_SIGNAL_OP_PARAMS}))")
+    out += _ctx_stamp(which, "SHMEM_CTX_DECL" if which == "shmem" else "SHMEMX_CTX_DECL",
+                      lambda f: f"SHMEM_CTX_DECL({f[3]}, {_ctx_name_tokens(f[4], f[5])}, (shmem_ctx_t ctx, {f[6]}))")
+    out += ["", "#ifdef __cplusplus", "}  /* extern \"C\" */", "#endif", ""]
+    out += _ctx_generics(which)
+    out += ["", f"#endif /* {guard} */", ""]
+    return "\n".join(out)
+
+
+def ctx_source():
+    out = ["// ctx_gen.cpp -- GENERATED by sos_amd/csrc/gen_bindings.py; do not edit.", "//",
+           "// libsos_amd_ctx.so: the six context management calls and the context twins of the typed, sized",
+           "// and mem forms of put / get / p / g / iput / iget / ibput / ibget, of the non-deprecated atomics",
+           "// and of put with signal and the signal operations (the shmem_ctx_* stamping of",
+           "// src/data_c.c4:820-880 and src/atomic_c.c4) over the sos_api_ctx_* entries of libsos_amd.so:",
+           "// strong pshmem_*, weak shmem_* aliases.  One macro per form, stamped over the type tables of",
+           "// shmem_ctx.h; `fn` is the entry's own name.",
+           '#include "shmem.h"', '#include "shmemx.h"', '#include "sosx.h"', '#include "api_internal.h"', "",
+           "#define SOS_CTX_DEF(ret, name, params, ...) \\",
+           "    ret p##name params { static const char fn[] = #name; (void)fn; __VA_ARGS__ } \\",
+           "    ret name params __attribute__((weak, alias(\"p\" #name)));", "", 'extern "C" {', ""]
+    for name, ret, params, body in CTX_MANAGEMENT:
+        out.append(f"SOS_CTX_DEF({ret}, {name}, ({params}), {body})")
+    for name, body in _CTX_SIGNAL_OPS:
+        out.append(f"SOS_CTX_DEF(void, {name}, (shmem_ctx_t ctx, {_CTX_SIGNAL_OP_PARAMS}), {body})")
+    for which in ("shmem", "shmemx"):
+        out += _ctx_stamp(which, "SOS_CTX_" + which.upper(),
+                          lambda f: f"SOS_CTX_DEF({f[3]}, {_ctx_name_tokens(f[4], f[5])}, (shmem_ctx_t ctx, {f[6]}), {f[7]})")
+    out += ["", '}  // extern "C"', ""]
+    return "\n".join(out)
+
+
 def collect_symbols():
     """The generated fcollect / alltoall / alltoalls names (typed forms only)."""
     return [f"shmem_{st}_{kind}" for kind in COLLECTS for st, ct in RMA]
@@ -959,6 +1247,12 @@ def main():
     targets[os.path.join(ROOT, "include", "shmem_signal.h")] = signal_header("signal")
     targets[os.path.join(ROOT, "include", "shmem_sync.h")] = signal_header("sync")
     targets[os.path.join(ROOT, "sos_amd", "csrc", "signal_gen.cpp")] = signal_source()
+    n_ctx_amo = sum(len(AMO_TABLES[t]) for t, _, _, _, dep in AMO_FORMS.values() if not dep)
+    n_ctx = len(CTX_MANAGEMENT) + (len(rma_symbols()) - 1) + n_ctx_amo + 2 * (len(RMA) + len(RMA_SIZES) + 1) + 2
+    assert len(ctx_symbols()) == len(set(ctx_symbols())) == n_ctx, (len(ctx_symbols()), n_ctx)
+    targets[os.path.join(ROOT, "include", "shmem_ctx.h")] = ctx_header("shmem")
+    targets[os.path.join(ROOT, "include", "shmemx_ctx.h")] = ctx_header("shmemx")
+    targets[os.path.join(ROOT, "sos_amd", "csrc", "ctx_gen.cpp")] = ctx_source()
     check = "--check" in sys.argv
     stale = False
     for path, text in targets.items():

@@ -122,7 +122,7 @@ Result step(int kind, const Where &w, long *lock, const char *fn)
                                         : soslock::hand_off<H>(w.data, &base, w.offset, 1, 0);
     } else {
         // the chain reads `last` on PE 0: after the acquire a wait may have left owed
-        before_peer_read(0, fn);
+        before_peer_read(default_ctx(), 0, fn);
         // SOS's quiet: the release kernel starts after a system-scope release of the
         // stream's earlier work
         if (kind == SOSX_LOCK_RELEASE) hip_check(release_system(s.stream), fn);

@@ -18,7 +18,8 @@
 //  * signal: the workgroup whose add returned gridDim.x - 1 is the last; its lane 0 performs
 //    the update -- a system-scope exchange (SET) or fetch_add (ADD), as amo.hip does an
 //    atomic -- and stores 0 to the ticket for the next launch.  Launches that share a ticket
-//    must be serial (the library's are: one stream).
+//    must be serial: the library stream's share the library's word, and every created
+//    context brings its own (sosx_put_signal_on).
 //
 // Nothing here waits on memory: no loop polls a word.
 //
@@ -96,10 +97,11 @@ namespace {
 unsigned *g_ticket = nullptr;
 
 template <class A, bool UL>
-int launch(char *dst, const char *src, const PsPlan &p, uint64_t *sig, uint64_t value, int sig_op, hipStream_t st)
+int launch(char *dst, const char *src, const PsPlan &p, uint64_t *sig, uint64_t value, int sig_op, unsigned *ticket,
+           hipStream_t st)
 {
     hipLaunchKernelGGL((k_put_signal<A, UL>), dim3(p.grid), dim3(kThreads), 0, st, dst, src, p, sig, value, sig_op,
-                       g_ticket);
+                       ticket);
     return hip_ok(hipGetLastError());
 }
 
@@ -116,29 +118,39 @@ template <class T> int snapshot(void *out, const void *ivars, size_t nelems, hip
 extern "C" int sosx_put_signal(void *target, const void *source, size_t nbytes, uint64_t *sig_addr, uint64_t signal,
                                int sig_op, void *stream)
 {
+    return sosx_put_signal_on(target, source, nbytes, sig_addr, signal, sig_op, nullptr, stream);
+}
+
+// The same launch counting arrivals on `ticket`, a zeroed device word the caller owns
+// (a context's: launches on different streams must not share one), or on the library's
+// own when null.
+extern "C" int sosx_put_signal_on(void *target, const void *source, size_t nbytes, uint64_t *sig_addr, uint64_t signal,
+                                  int sig_op, unsigned *ticket, void *stream)
+{
     // every argument is checked before any device work
     if (!sig_addr || (uintptr_t)sig_addr % sizeof(uint64_t)) return SOSX_ERR_ARG;
     if (sig_op != SOSX_SIGNAL_SET && sig_op != SOSX_SIGNAL_ADD) return SOSX_ERR_ARG;
     if (nbytes && (!target || !source)) return SOSX_ERR_ARG;
     if (nbytes > SIZE_MAX / 2) return SOSX_ERR_ARG;
-    if (!g_ticket) {
+    if (!ticket && !g_ticket) {
         if (hipMalloc((void **)&g_ticket, sizeof(unsigned)) != hipSuccess) {
             g_ticket = nullptr;
             return SOSX_ERR_HIP;
         }
         if (hipMemset(g_ticket, 0, sizeof(unsigned)) != hipSuccess) return SOSX_ERR_HIP;
     }
+    if (!ticket) ticket = g_ticket;
     const PsPlan p = ps_plan((uintptr_t)target, (uintptr_t)source, nbytes);
     char *d = (char *)target;
     const char *s = (const char *)source;
     hipStream_t st = as_stream(stream);
-    if (p.unaligned_loads) return launch<u32x4, true>(d, s, p, sig_addr, signal, sig_op, st);
+    if (p.unaligned_loads) return launch<u32x4, true>(d, s, p, sig_addr, signal, sig_op, ticket, st);
     switch (p.width) {
-        case 16: return launch<u32x4, false>(d, s, p, sig_addr, signal, sig_op, st);
-        case 8: return launch<uint64_t, false>(d, s, p, sig_addr, signal, sig_op, st);
-        case 4: return launch<uint32_t, false>(d, s, p, sig_addr, signal, sig_op, st);
-        case 2: return launch<uint16_t, false>(d, s, p, sig_addr, signal, sig_op, st);
-        case 1: return launch<uint8_t, false>(d, s, p, sig_addr, signal, sig_op, st);
+        case 16: return launch<u32x4, false>(d, s, p, sig_addr, signal, sig_op, ticket, st);
+        case 8: return launch<uint64_t, false>(d, s, p, sig_addr, signal, sig_op, ticket, st);
+        case 4: return launch<uint32_t, false>(d, s, p, sig_addr, signal, sig_op, ticket, st);
+        case 2: return launch<uint16_t, false>(d, s, p, sig_addr, signal, sig_op, ticket, st);
+        case 1: return launch<uint8_t, false>(d, s, p, sig_addr, signal, sig_op, ticket, st);
         default: return SOSX_ERR_ARG;
     }
 }

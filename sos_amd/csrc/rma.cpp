@@ -20,7 +20,10 @@
 //    completion at once; the nbi forms only enqueue, and shmem_quiet / shmem_fence / every
 //    barrier and sync complete the stream with a system-scope release;
 //  * visibility, consumer half: a launch that reads a peer's heap follows an acquire
-//    issued after the last wait for a peer (acquire_system; note_peer_read counts it).
+//    issued after the last wait for a peer (acquire_system; note_peer_read counts it);
+//  * contexts: "the library stream" above is the stream of the context the call names --
+//    SHMEM_CTX_DEFAULT for the plain forms -- with that context's release event, stage and
+//    acquire flag (ctx.cpp).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -179,12 +182,11 @@ char *sosrt::translate(const void *remote, int pe)
 
 // Before a launch or copy that reads peer `pe`'s heap: the acquire a wait since the last
 // one left owed, and the read counted.
-void sosrt::before_peer_read(int pe, const char *fn)
+void sosrt::before_peer_read(Ctx &c, int pe, const char *fn)
 {
-    State &s = st();
-    if (pe == s.my_pe) return;
-    if (s.acq_pending) hip_check(acquire_system(s.stream), fn);
-    note_peer_read(false);
+    if (pe == st().my_pe) return;
+    if (c.acq_pending) hip_check(acquire_system(c), fn);  // on the stream that does the read
+    note_peer_read(c, false);
 }
 
 // The address at which a kernel on this PE's GPU reaches the `bytes` bytes at p, or null
@@ -210,15 +212,15 @@ char *sosrt::device_view(const void *p, size_t bytes)
 
 namespace {
 
-void contiguous(void *dst, const void *src, size_t bytes, int read_pe, bool nbi, const char *fn)
+void contiguous(Ctx &c, void *dst, const void *src, size_t bytes, int read_pe, bool nbi, const char *fn)
 {
-    State &s = st();
     if (!bytes) return;
-    before_peer_read(read_pe, fn);
+    ++c.enqueued;
+    before_peer_read(c, read_pe, fn);
     // the copy engine reads HBM: what the stream's kernels stored goes there first
-    hip_check(release_system(s.stream), fn);
-    hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, s.stream), fn);
-    if (!nbi) hip_check(sync_system(s.stream), fn);
+    hip_check(release_system(c), fn);
+    hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, c.stream), fn);
+    if (!nbi) hip_check(sync_system(c), fn);
 }
 
 size_t span_bytes(size_t bsize, size_t nblocks, ptrdiff_t stride, size_t ts)
@@ -231,105 +233,124 @@ size_t span_bytes(size_t bsize, size_t nblocks, ptrdiff_t stride, size_t ts)
 // pe == my_pe the remote side may be static data that is not registered with HIP
 // (SHMEMX_REGISTER_DATA=0, a refused registration, the rounded-off first page).  Such a
 // side is packed into / unpacked from stage() by a 2-D copy, which touches the blocks only.
-void blocks(char *dst, ptrdiff_t dstr, const char *src, ptrdiff_t sstr, size_t bsize, size_t nblocks,
+void blocks(Ctx &c, char *dst, ptrdiff_t dstr, const char *src, ptrdiff_t sstr, size_t bsize, size_t nblocks,
             size_t ts, int read_pe, const char *fn)
 {
-    State &s = st();
     if (!bsize || !nblocks) return;
+    ++c.enqueued;
     const size_t bbytes = bsize * ts;
     char *ddev = device_view(dst, span_bytes(bsize, nblocks, dstr, ts));
     const char *sdev = device_view(src, span_bytes(bsize, nblocks, sstr, ts));
     int rc = SOSX_OK;
     if (ddev && sdev) {
-        before_peer_read(read_pe, fn);
-        rc = sosx_block_strided_copy(ddev, dstr, sdev, sstr, bsize, nblocks, ts, s.stream);
+        before_peer_read(c, read_pe, fn);
+        rc = sosx_block_strided_copy(ddev, dstr, sdev, sstr, bsize, nblocks, ts, c.stream);
     } else if (ddev) {
         // pageable source: pack the blocks into the stage, then the kernel
-        char *stg = (char *)stage(bbytes * nblocks);
+        char *stg = (char *)stage(c, bbytes * nblocks);
         hip_check(hipMemcpy2DAsync(stg, bbytes, src, (size_t)sstr * ts, bbytes, nblocks, hipMemcpyHostToDevice,
-                                   s.stream), fn);
-        rc = sosx_block_strided_copy(ddev, dstr, stg, (ptrdiff_t)bsize, bsize, nblocks, ts, s.stream);
+                                   c.stream), fn);
+        rc = sosx_block_strided_copy(ddev, dstr, stg, (ptrdiff_t)bsize, bsize, nblocks, ts, c.stream);
     } else if (sdev) {
         // pageable target: the kernel packs into the stage, a 2-D copy writes the blocks
-        char *stg = (char *)stage(bbytes * nblocks);
-        before_peer_read(read_pe, fn);
-        rc = sosx_block_strided_copy(stg, (ptrdiff_t)bsize, sdev, sstr, bsize, nblocks, ts, s.stream);
+        char *stg = (char *)stage(c, bbytes * nblocks);
+        before_peer_read(c, read_pe, fn);
+        rc = sosx_block_strided_copy(stg, (ptrdiff_t)bsize, sdev, sstr, bsize, nblocks, ts, c.stream);
         if (rc == SOSX_OK) {
-            hip_check(release_system(s.stream), fn);  // the copy engine reads HBM
+            hip_check(release_system(c), fn);  // the copy engine reads HBM
             hip_check(hipMemcpy2DAsync(dst, (size_t)dstr * ts, stg, bbytes, bbytes, nblocks,
-                                       hipMemcpyDeviceToHost, s.stream), fn);
+                                       hipMemcpyDeviceToHost, c.stream), fn);
         }
     } else {
         // both in pageable host memory of this process (pe == my_pe): the host moves the
         // blocks, after what the stream still has queued
-        hip_check(sync_system(s.stream), fn);
+        hip_check(sync_system(c), fn);
         for (size_t i = 0; i < nblocks; ++i)
             memcpy(dst + i * (size_t)dstr * ts, src + i * (size_t)sstr * ts, bbytes);
     }
     if (rc != SOSX_OK) raise_error("%s: block copy failed (%d)", fn, rc);
-    hip_check(sync_system(s.stream), fn);
+    hip_check(sync_system(c), fn);
 }
 
-void put_blocks(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+void put_blocks(Ctx &c, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize, size_t nblocks,
                 size_t ts, int pe, bool strided, const char *fn)
 {
     const sos_rma_op op = {dest, source, tst, sst, bsize, nblocks, ts, pe, 1, strided};
     checked(op, fn);
     if (!bsize || !nblocks) return;
-    blocks(translate(dest, pe), tst, (const char *)source, sst, bsize, nblocks, ts, st().my_pe, fn);
+    blocks(c, translate(dest, pe), tst, (const char *)source, sst, bsize, nblocks, ts, st().my_pe, fn);
 }
 
-void get_blocks(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+void get_blocks(Ctx &c, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize, size_t nblocks,
                 size_t ts, int pe, bool strided, const char *fn)
 {
     const sos_rma_op op = {source, dest, sst, tst, bsize, nblocks, ts, pe, 0, strided};
     checked(op, fn);
     if (!bsize || !nblocks) return;
-    blocks((char *)dest, tst, translate(source, pe), sst, bsize, nblocks, ts, pe, fn);
+    blocks(c, (char *)dest, tst, translate(source, pe), sst, bsize, nblocks, ts, pe, fn);
+}
+
+void put_on(Ctx &c, void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi, const char *fn)
+{
+    const sos_rma_op op = {dest, source, (ptrdiff_t)nelems, (ptrdiff_t)nelems, nelems, 1, type_size, pe, 1, 0};
+    checked(op, fn);
+    if (nelems) contiguous(c, translate(dest, pe), source, nelems * type_size, st().my_pe, nbi != 0, fn);
+}
+
+void get_on(Ctx &c, void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi, const char *fn)
+{
+    const sos_rma_op op = {source, dest, (ptrdiff_t)nelems, (ptrdiff_t)nelems, nelems, 1, type_size, pe, 0, 0};
+    checked(op, fn);
+    if (nelems) contiguous(c, dest, translate(source, pe), nelems * type_size, pe, nbi != 0, fn);
 }
 
 }  // namespace
 
+// put on a context, for put-with-signal's composed form (signal.cpp)
+void sosrt::rma_put_on(Ctx &c, void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi,
+                       const char *fn)
+{
+    put_on(c, dest, source, nelems, type_size, pe, nbi, fn);
+}
+
+// Every entry twice: on SHMEM_CTX_DEFAULT, and on the context the program names, whose
+// `pe` is an index of its team (ctx_checked translates it before the checks).
 extern "C" {
 
 void sos_api_put(void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi,
                  const char *fn)
 {
-    const sos_rma_op op = {dest, source, (ptrdiff_t)nelems, (ptrdiff_t)nelems, nelems, 1, type_size, pe, 1, 0};
-    checked(op, fn);
-    if (nelems) contiguous(translate(dest, pe), source, nelems * type_size, st().my_pe, nbi != 0, fn);
+    put_on(default_ctx(), dest, source, nelems, type_size, pe, nbi, fn);
 }
 
 void sos_api_get(void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi,
                  const char *fn)
 {
-    const sos_rma_op op = {source, dest, (ptrdiff_t)nelems, (ptrdiff_t)nelems, nelems, 1, type_size, pe, 0, 0};
-    checked(op, fn);
-    if (nelems) contiguous(dest, translate(source, pe), nelems * type_size, pe, nbi != 0, fn);
+    get_on(default_ctx(), dest, source, nelems, type_size, pe, nbi, fn);
 }
 
 void sos_api_iput(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
                   size_t type_size, int pe, const char *fn)
 {
-    put_blocks(dest, source, tst, sst, 1, nelems, type_size, pe, true, fn);
+    put_blocks(default_ctx(), dest, source, tst, sst, 1, nelems, type_size, pe, true, fn);
 }
 
 void sos_api_iget(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
                   size_t type_size, int pe, const char *fn)
 {
-    get_blocks(dest, source, tst, sst, 1, nelems, type_size, pe, true, fn);
+    get_blocks(default_ctx(), dest, source, tst, sst, 1, nelems, type_size, pe, true, fn);
 }
 
 void sos_api_ibput(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize,
                    size_t nblocks, size_t type_size, int pe, const char *fn)
 {
-    put_blocks(dest, source, tst, sst, bsize, nblocks, type_size, pe, false, fn);
+    put_blocks(default_ctx(), dest, source, tst, sst, bsize, nblocks, type_size, pe, false, fn);
 }
 
 void sos_api_ibget(void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize,
                    size_t nblocks, size_t type_size, int pe, const char *fn)
 {
-    get_blocks(dest, source, tst, sst, bsize, nblocks, type_size, pe, false, fn);
+    get_blocks(default_ctx(), dest, source, tst, sst, bsize, nblocks, type_size, pe, false, fn);
 }
 
 void sos_api_p(void *addr, const void *value, size_t type_size, int pe, const char *fn)
@@ -340,6 +361,58 @@ void sos_api_p(void *addr, const void *value, size_t type_size, int pe, const ch
 void sos_api_g(void *value, const void *addr, size_t type_size, int pe, const char *fn)
 {
     sos_api_get(value, addr, 1, type_size, pe, 0, fn);
+}
+
+void sos_api_ctx_put(shmem_ctx_t ctx, void *dest, const void *source, size_t nelems, size_t type_size, int pe,
+                     int nbi, const char *fn)
+{
+    Ctx &c = ctx_checked(ctx, &pe, fn);
+    put_on(c, dest, source, nelems, type_size, pe, nbi, fn);
+}
+
+void sos_api_ctx_get(shmem_ctx_t ctx, void *dest, const void *source, size_t nelems, size_t type_size, int pe,
+                     int nbi, const char *fn)
+{
+    Ctx &c = ctx_checked(ctx, &pe, fn);
+    get_on(c, dest, source, nelems, type_size, pe, nbi, fn);
+}
+
+void sos_api_ctx_iput(shmem_ctx_t ctx, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      size_t type_size, int pe, const char *fn)
+{
+    Ctx &c = ctx_checked(ctx, &pe, fn);
+    put_blocks(c, dest, source, tst, sst, 1, nelems, type_size, pe, true, fn);
+}
+
+void sos_api_ctx_iget(shmem_ctx_t ctx, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t nelems,
+                      size_t type_size, int pe, const char *fn)
+{
+    Ctx &c = ctx_checked(ctx, &pe, fn);
+    get_blocks(c, dest, source, tst, sst, 1, nelems, type_size, pe, true, fn);
+}
+
+void sos_api_ctx_ibput(shmem_ctx_t ctx, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize,
+                       size_t nblocks, size_t type_size, int pe, const char *fn)
+{
+    Ctx &c = ctx_checked(ctx, &pe, fn);
+    put_blocks(c, dest, source, tst, sst, bsize, nblocks, type_size, pe, false, fn);
+}
+
+void sos_api_ctx_ibget(shmem_ctx_t ctx, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t sst, size_t bsize,
+                       size_t nblocks, size_t type_size, int pe, const char *fn)
+{
+    Ctx &c = ctx_checked(ctx, &pe, fn);
+    get_blocks(c, dest, source, tst, sst, bsize, nblocks, type_size, pe, false, fn);
+}
+
+void sos_api_ctx_p(shmem_ctx_t ctx, void *addr, const void *value, size_t type_size, int pe, const char *fn)
+{
+    sos_api_ctx_put(ctx, addr, value, 1, type_size, pe, 0, fn);
+}
+
+void sos_api_ctx_g(shmem_ctx_t ctx, void *value, const void *addr, size_t type_size, int pe, const char *fn)
+{
+    sos_api_ctx_get(ctx, value, addr, 1, type_size, pe, 0, fn);
 }
 
 void *sos_api_ptr(const void *dest, int pe)

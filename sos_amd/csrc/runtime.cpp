@@ -529,13 +529,13 @@ static void *grow(void **buf, size_t *have, size_t need, const char *what)
 hipError_t release_system(hipStream_t stream)
 {
     State &s = st();
-    if (!s.sys_ev) {
+    if (!s.def_ctx.sys_ev) {
         const hipError_t e =
-            hipEventCreateWithFlags(&s.sys_ev, hipEventReleaseToSystem | hipEventDisableTiming);
+            hipEventCreateWithFlags(&s.def_ctx.sys_ev, hipEventReleaseToSystem | hipEventDisableTiming);
         if (e != hipSuccess) return e;
     }
     ++s.sys_releases;
-    return hipEventRecord(s.sys_ev, stream);
+    return hipEventRecord(s.def_ctx.sys_ev, stream);
 }
 
 hipError_t acquire_system(hipStream_t stream)
@@ -548,18 +548,24 @@ hipError_t acquire_system(hipStream_t stream)
     }
     ++s.sys_acquires;
     ++s.acquire_kernels;
-    s.acq_pending = false;
+    s.def_ctx.acq_pending = false;
     return sosx_acquire_system(s.acq_mask, stream) == SOSX_OK ? hipSuccess : hipErrorLaunchFailure;
 }
 
-void note_peer_wait() { st().acq_pending = true; }
+// every live context owes one: an acquire on one stream says nothing about another
+void note_peer_wait()
+{
+    State &s = st();
+    s.def_ctx.acq_pending = true;
+    for (Ctx *c : s.ctxs) c->acq_pending = true;
+}
 
 void note_peer_read(bool own_acquire)
 {
     State &s = st();
     ++s.peer_reads;
     if (own_acquire) ++s.sys_acquires;
-    else if (s.acq_pending) ++s.peer_reads_unacquired;
+    else if (s.def_ctx.acq_pending) ++s.peer_reads_unacquired;
 }
 
 // The release event, then a stream synchronisation: it waits for the event too, and
@@ -575,14 +581,14 @@ hipError_t sync_system(hipStream_t stream)
         const char *v = getenv("SOSX_TEST_EVENT_WAIT");
         return v && *v == '1';
     }();
-    if (event_wait) return e == hipSuccess ? hipEventSynchronize(st().sys_ev) : e;
+    if (event_wait) return e == hipSuccess ? hipEventSynchronize(st().def_ctx.sys_ev) : e;
 #endif
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     return e;
 }
 
 void *scratch(size_t bytes) { return grow(&st().scratch, &st().scratch_bytes, bytes, "hipMalloc(scratch)"); }
-void *stage(size_t bytes) { return grow(&st().stage, &st().stage_bytes, bytes, "hipMalloc(stage)"); }
+void *stage(size_t bytes) { return grow(&st().def_ctx.stage, &st().def_ctx.stage_bytes, bytes, "hipMalloc(stage)"); }
 
 bool is_device_ptr(const void *p)
 {
@@ -743,6 +749,7 @@ static void init_common(int pe, int npes, const ncclUniqueId *uid)
     s.node = s.world;    // SHMEMX_TEAM_NODE (:101-164)
     s.node.psync_idx = 2;
     SHMEM_TEAM_WORLD = team_handle(&s.world);
+    SHMEM_CTX_DEFAULT = reinterpret_cast<shmem_ctx_t>(&default_ctx());
     SHMEM_TEAM_SHARED = team_handle(&s.shared);
     SHMEMX_TEAM_NODE = team_handle(&s.node);
     // team slots (src/shmem_team.c:171-226): 64 at most, 3 at least, 0..2 predefined
@@ -879,6 +886,9 @@ void shmem_finalize(void)
 {
     State &s = st();
     if (!s.initialized) return;
+    // quiet and destroy the contexts the program left, before the barrier: what they still
+    // had queued is delivered when the peers leave it
+    ctx_destroy_all();
     team_barrier(s.world);
     // destroy the teams the program left (src/shmem_team.c:238-247)
     for (size_t i = 3; i < s.team_pool.size(); ++i)
@@ -890,10 +900,10 @@ void shmem_finalize(void)
     if (s.comm) ncclCommDestroy(s.comm);
     s.comm = nullptr;
     if (s.scratch) (void)hipFree(s.scratch);
-    if (s.stage) (void)hipFree(s.stage);
+    if (s.def_ctx.stage) (void)hipFree(s.def_ctx.stage);
     if (s.dbar) (void)hipFree(s.dbar);
-    s.scratch = s.stage = nullptr;
-    s.scratch_bytes = s.stage_bytes = 0;
+    s.scratch = s.def_ctx.stage = nullptr;
+    s.scratch_bytes = s.def_ctx.stage_bytes = 0;
     s.dbar = nullptr;
     sosx_combine_host_release();
     small_local_release();
@@ -910,8 +920,8 @@ void shmem_finalize(void)
             if (e) (void)hipEventDestroy(e);
             e = nullptr;
         }
-    if (s.sys_ev) (void)hipEventDestroy(s.sys_ev);
-    s.sys_ev = nullptr;
+    if (s.def_ctx.sys_ev) (void)hipEventDestroy(s.def_ctx.sys_ev);
+    s.def_ctx.sys_ev = nullptr;
     unregister_data_segment(s);
     if (s.acq_mask) (void)hipFree(s.acq_mask);
     s.acq_mask = nullptr;
@@ -1178,11 +1188,11 @@ size_t sosx_release_workspaces(void)
     State &s = st();
     if (!s.initialized) return 0;
     hip_check(hipStreamSynchronize(s.stream), "hipStreamSynchronize");
-    const size_t had = (s.scratch ? s.scratch_bytes : 0) + (s.stage ? s.stage_bytes : 0);
+    const size_t had = (s.scratch ? s.scratch_bytes : 0) + (s.def_ctx.stage ? s.def_ctx.stage_bytes : 0);
     if (s.scratch) hip_check(hipFree(s.scratch), "hipFree(scratch)");
-    if (s.stage) hip_check(hipFree(s.stage), "hipFree(stage)");
-    s.scratch = s.stage = nullptr;
-    s.scratch_bytes = s.stage_bytes = 0;
+    if (s.def_ctx.stage) hip_check(hipFree(s.def_ctx.stage), "hipFree(stage)");
+    s.scratch = s.def_ctx.stage = nullptr;
+    s.scratch_bytes = s.def_ctx.stage_bytes = 0;
     return had;
 }
 
@@ -1505,6 +1515,7 @@ void shmem_team_destroy(shmem_team_t team)
         raise_error("Cannot destroy a pre-defined team");
     Team *t = team_from_handle(team);
     if (!t || t->predefined) return;
+    ctx_destroy_team(t);  // quiets them first (src/shmem_team.c:518-528)
     if (t->psync_idx >= 3 && t->psync_idx < (int)s.team_pool.size() && s.team_pool[(size_t)t->psync_idx] == t) {
         s.team_pool[(size_t)t->psync_idx] = nullptr;
         s.team_avail |= 1ull << t->psync_idx;

@@ -65,6 +65,32 @@ struct Heap {
     }
 };
 
+// A communication context (shmem_ctx_t, ctx.cpp): one ordering
+// domain with its own completion.  Everything that would otherwise be shared between two
+// streams is the context's: the stream, the system-scope release event, the pack / unpack
+// staging buffer, the nbi atomics' fetch ring, put-with-signal's ticket word and the
+// "acquire owed" flag.  State::def_ctx is SHMEM_CTX_DEFAULT over the library stream.
+struct Ctx {
+    bool is_default = false;
+    long options = 0;                 // SHMEM_CTX_* bits given at creation
+    Team *team = nullptr;             // shmem_ctx_get_team's answer; not dereferenced after creation
+    int t_start = 0, t_stride = 1, t_size = 1;  // that team's PEs: what a `pe` argument indexes
+    int slot = -1;                    // stream-pool slot (-1: the library stream)
+    hipStream_t stream = nullptr;     // the default context's follows State::stream
+    hipEvent_t sys_ev = nullptr;      // system-scope release marker (sync_system)
+    void *stage = nullptr;            // staging for pageable sides of the block copies
+    size_t stage_bytes = 0;
+    uint64_t *amo_ring = nullptr;     // device slots of nbi atomics' old values (amo.cpp)
+    unsigned amo_ring_used = 0;
+    unsigned *ticket = nullptr;       // put-with-signal's arrival counter (putsignal.hip)
+    bool acq_pending = false;         // a peer wait since this context's last acquire
+    // what the library did on this context (sosx_ctx_stats, test build)
+    long enqueued = 0;                // operations issued on it
+    long completed = 0;               // of those, completed by a stream synchronisation
+    long releases = 0;                // records of sys_ev
+    long syncs = 0;                   // host waits for its stream
+};
+
 struct State {
     bool initialized = false;
     bool finalized = false;
@@ -78,19 +104,15 @@ struct State {
     // device workspaces, grown on demand
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
-    void *stage = nullptr;            // staging for host-resident source/target
-    size_t stage_bytes = 0;
     int *dbar = nullptr;              // 1-int device word for barriers
     // host-resident ring reductions, pipelined in stripes (executor.cpp): copy streams,
     // per-slot events, three device stripe slots (the RCCL path's; p2p uses the stage)
     hipStream_t pipe_h2d = nullptr, pipe_d2h = nullptr;
     hipEvent_t pipe_ev[3][3] = {};    // [slot][h2d done, exchange done, d2h done]
-    hipEvent_t sys_ev = nullptr;      // system-scope release marker (sync_system)
     long sys_releases = 0;            // how many sync_system / release_system markers ran
     // consumer half of the visibility rule (acquire_system, note_peer_wait/read)
     long sys_acquires = 0, peer_reads = 0, peer_reads_unacquired = 0;
     long acquire_kernels = 0;         // of sys_acquires: stream-wide acquire kernels
-    bool acq_pending = false;         // a peer wait since the last acquire (stream order)
     unsigned *acq_mask = nullptr;     // device word: XCD ids the acquire kernels ran on
     uint64_t *collect_lens = nullptr; // pinned: collect's internal lengths fcollect (api.cpp)
     void *stripes = nullptr;
@@ -137,6 +159,14 @@ struct State {
     long teams_max = 10;
     uint64_t team_avail = 0;
     std::vector<Team *> team_pool;
+    // contexts (ctx.cpp): the default one holds the library stream's release event, stage
+    // and acquire flag; created ones take streams from a pool of ctx_streams (round-robin)
+    Ctx def_ctx;
+    std::vector<Ctx *> ctxs;              // live created contexts
+    std::vector<hipStream_t> ctx_pool;    // created on first use, SHMEMX_CTX_STREAMS of them
+    int ctx_streams = 3;
+    unsigned long ctx_created = 0;        // ever created: the round-robin position
+    std::vector<const void *> ctx_dead;   // handles destroyed and not reused (for the message)
     std::mutex mu;
 };
 
@@ -166,6 +196,9 @@ void nccl_check(ncclResult_t r, const char *what);
 hipError_t sync_system(hipStream_t stream);
 // The same release in stream order, without a host wait (stream-mode p2p posts).
 hipError_t release_system(hipStream_t stream);
+// The two on a context: its own event on its own stream (ctx.cpp).
+hipError_t sync_system(Ctx &c);
+hipError_t release_system(Ctx &c);
 
 // The consumer half: a launch that reads bytes a peer published
 // must follow, in stream order, a system-scope acquire issued after the wait that saw the
@@ -180,10 +213,27 @@ hipError_t release_system(hipStream_t stream);
 hipError_t acquire_system(hipStream_t stream);
 void note_peer_wait();
 void note_peer_read(bool own_acquire);
+// Across contexts: note_peer_wait leaves EVERY live context owing an acquire (an acquire on
+// one stream says nothing about another); the stream form above pays the default
+// context's, these pay and check `c`'s, on the stream that does the read.
+hipError_t acquire_system(Ctx &c);
+void note_peer_read(Ctx &c, bool own_acquire);
 
 // Device workspaces (grown, never shrunk).
 void *scratch(size_t bytes);
 void *stage(size_t bytes);
+void *stage(Ctx &c, size_t bytes);   // the context's own, reused in its stream's order
+
+// Contexts (ctx.cpp).  default_ctx: SHMEM_CTX_DEFAULT's object, its stream brought up to
+// State::stream.  ctx_checked: the object behind a handle the program passed -- refused
+// through raise_error when invalid or destroyed, never dereferenced -- with *pe translated
+// from an index of the context's team to a world PE.  ctx_destroy_team / ctx_destroy_all:
+// quiet and free a team's non-private contexts (shmem_team_destroy) / every context
+// (shmem_finalize).
+Ctx &default_ctx();
+Ctx &ctx_checked(shmem_ctx_t handle, int *pe, const char *fn);
+void ctx_destroy_team(Team *t);
+void ctx_destroy_all();
 
 // Is `p` a device (HBM) pointer?  Host pageable, pinned and static data are not.
 bool is_device_ptr(const void *p);

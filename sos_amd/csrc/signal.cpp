@@ -227,6 +227,52 @@ struct Sync {
     }
 };
 
+// put with signal on context `c` (pe: a world PE).  The fused launch counts arrivals on
+// the context's own ticket word: launches that share a ticket must be serial, and two
+// contexts' streams are not.
+void put_signal_on(Ctx &c, void *dest, const void *source, size_t nelems, size_t type_size, uint64_t *sig_addr,
+                   uint64_t signal, int sig_op, int pe, int nbi, const char *fn)
+{
+    State &s = st();
+    {
+        RmaLayout lay;
+        rma_layout_now(lay);
+        const sos_put_signal_op op = {dest, source, sig_addr, nelems, type_size, sig_op, pe};
+        char msg[512];
+        if (sos_put_signal_check(&lay.l, &op, msg, sizeof(msg)) != SOS_RMA_OK) raise_error("%s: %s", fn, msg);
+    }
+    const size_t bytes = nelems * type_size;
+    const char *sdev = nullptr;
+    const bool fused = bytes <= fused_max() && s.dev_heap.contains(sig_addr, sizeof(uint64_t)) &&
+                       (!bytes || (s.dev_heap.contains(dest, bytes) && (sdev = device_view(source, bytes))));
+    if (fused) {
+        ++sig().fused_calls;
+        ++c.enqueued;
+        if (!c.is_default && !c.ticket) {
+            hip_check(hipMalloc((void **)&c.ticket, sizeof(unsigned)), "hipMalloc(put-signal ticket)");
+            hip_check(hipMemsetAsync(c.ticket, 0, sizeof(unsigned), c.stream), "hipMemsetAsync(put-signal ticket)");
+        }
+        const int rc = sosx_put_signal_on(bytes ? translate(dest, pe) : nullptr, sdev, bytes,
+                                          (uint64_t *)translate(sig_addr, pe), signal, sig_op, c.ticket, c.stream);
+        if (rc != SOSX_OK) raise_error("%s: put-with-signal launch failed (%d)", fn, rc);
+    } else {
+        ++sig().composed_calls;
+        rma_put_on(c, dest, source, nelems, type_size, pe, 1, fn);
+        hip_check(release_system(c), fn);
+        amo_on(c, sig_op == SOSX_SIGNAL_ADD ? SOSX_AMO_ADD : SOSX_AMO_SET, sig_addr, &signal, nullptr, nullptr, 0,
+               sizeof(uint64_t), 0, pe, 0, fn);
+    }
+    if (!nbi) hip_check(sync_system(c), fn);
+}
+
+void signal_op_on(Ctx &c, uint64_t *sig_addr, uint64_t signal, int sig_op, int pe, const char *fn)
+{
+    if (sig_op != SOSX_SIGNAL_SET && sig_op != SOSX_SIGNAL_ADD)
+        raise_error("%s: Argument \"sig_op\", invalid atomic operation for signal (%d)", fn, sig_op);
+    amo_on(c, sig_op == SOSX_SIGNAL_ADD ? SOSX_AMO_ADD : SOSX_AMO_SET, sig_addr, &signal, nullptr, nullptr, 0,
+           sizeof(uint64_t), 0, pe, 0, fn);
+}
+
 }  // namespace
 
 void sosrt::signal_release()
@@ -257,39 +303,25 @@ void sosx_signal_stats(long *fused, long *composed, long *probes)
 void sos_api_put_signal(void *dest, const void *source, size_t nelems, size_t type_size, uint64_t *sig_addr,
                         uint64_t signal, int sig_op, int pe, int nbi, const char *fn)
 {
-    State &s = st();
-    {
-        RmaLayout lay;
-        rma_layout_now(lay);
-        const sos_put_signal_op op = {dest, source, sig_addr, nelems, type_size, sig_op, pe};
-        char msg[512];
-        if (sos_put_signal_check(&lay.l, &op, msg, sizeof(msg)) != SOS_RMA_OK) raise_error("%s: %s", fn, msg);
-    }
-    const size_t bytes = nelems * type_size;
-    const char *sdev = nullptr;
-    const bool fused = bytes <= fused_max() && s.dev_heap.contains(sig_addr, sizeof(uint64_t)) &&
-                       (!bytes || (s.dev_heap.contains(dest, bytes) && (sdev = device_view(source, bytes))));
-    if (fused) {
-        ++sig().fused_calls;
-        const int rc = sosx_put_signal(bytes ? translate(dest, pe) : nullptr, sdev, bytes,
-                                       (uint64_t *)translate(sig_addr, pe), signal, sig_op, s.stream);
-        if (rc != SOSX_OK) raise_error("%s: put-with-signal launch failed (%d)", fn, rc);
-    } else {
-        ++sig().composed_calls;
-        sos_api_put(dest, source, nelems, type_size, pe, 1, fn);
-        hip_check(release_system(s.stream), fn);
-        sos_api_amo(sig_op == SOSX_SIGNAL_ADD ? SOSX_AMO_ADD : SOSX_AMO_SET, sig_addr, &signal, nullptr, nullptr, 0,
-                    sizeof(uint64_t), 0, pe, 0, fn);
-    }
-    if (!nbi) hip_check(sync_system(s.stream), fn);
+    put_signal_on(default_ctx(), dest, source, nelems, type_size, sig_addr, signal, sig_op, pe, nbi, fn);
+}
+
+void sos_api_ctx_put_signal(shmem_ctx_t ctx, void *dest, const void *source, size_t nelems, size_t type_size,
+                            uint64_t *sig_addr, uint64_t signal, int sig_op, int pe, int nbi, const char *fn)
+{
+    Ctx &c = ctx_checked(ctx, &pe, fn);
+    put_signal_on(c, dest, source, nelems, type_size, sig_addr, signal, sig_op, pe, nbi, fn);
 }
 
 void sos_api_signal_op(uint64_t *sig_addr, uint64_t signal, int sig_op, int pe, const char *fn)
 {
-    if (sig_op != SOSX_SIGNAL_SET && sig_op != SOSX_SIGNAL_ADD)
-        raise_error("%s: Argument \"sig_op\", invalid atomic operation for signal (%d)", fn, sig_op);
-    sos_api_amo(sig_op == SOSX_SIGNAL_ADD ? SOSX_AMO_ADD : SOSX_AMO_SET, sig_addr, &signal, nullptr, nullptr, 0,
-                sizeof(uint64_t), 0, pe, 0, fn);
+    signal_op_on(default_ctx(), sig_addr, signal, sig_op, pe, fn);
+}
+
+void sos_api_ctx_signal_op(shmem_ctx_t ctx, uint64_t *sig_addr, uint64_t signal, int sig_op, int pe, const char *fn)
+{
+    Ctx &c = ctx_checked(ctx, &pe, fn);
+    signal_op_on(c, sig_addr, signal, sig_op, pe, fn);
 }
 
 uint64_t sos_api_signal_fetch(const uint64_t *sig_addr, const char *fn)

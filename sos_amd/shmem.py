@@ -8,6 +8,7 @@ SOS-style message.  Buffers are raw addresses (ints): device pointers (e.g. a to
 tensor's ``data_ptr()``) run in place on the GPU; host addresses are staged.
 """
 import ctypes
+import os
 import re
 
 from . import _lib
@@ -151,9 +152,29 @@ _RUNTIME = {
                                   _c.c_void_p, _c.c_void_p]),
     "sosx_lock_table": (_c.c_void_p, [_c.POINTER(_c.c_int)]),
     "sosx_lock_stats": (None, [_c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
+    # communication contexts: the checks and the pool's size (ctx.cpp, ctx_checks.cpp); the public
+    # names are _CTX_RUNTIME's and __getattr__'s, from libsos_amd_ctx.so
+    "sos_ctx_check": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.c_char_p,
+                                 _c.c_size_t]),
+    "sos_ctx_options_check": (_c.c_int, [_c.c_long, _c.c_char_p, _c.c_size_t]),
+    "sos_ctx_pool_size": (_c.c_int, [_c.c_char_p, _c.c_char_p, _c.c_size_t]),
+    "sos_ctx_stream_slot": (_c.c_int, [_c.c_ulong, _c.c_int]),
+    "sosx_ctx_streams": (_c.c_int, []),
+    "sosx_put_signal_on": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_uint64, _c.c_int,
+                                      _c.c_void_p, _c.c_void_p]),
     "sosx_prof_enable": (None, [_c.c_int]),
     "sosx_prof_get": (None, [_c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                              _c.POINTER(_c.c_long), _c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
+}
+
+# the context management calls (libsos_amd_ctx.so); the ctx twins of the typed calls resolve in __getattr__
+_CTX_RUNTIME = {
+    "shmem_ctx_create": (_c.c_int, [_c.c_long, _c.POINTER(_c.c_void_p)]),
+    "shmem_ctx_destroy": (None, [_c.c_void_p]),
+    "shmem_ctx_quiet": (None, [_c.c_void_p]),
+    "shmem_ctx_fence": (None, [_c.c_void_p]),
+    "shmem_team_create_ctx": (_c.c_int, [_c.c_void_p, _c.c_long, _c.POINTER(_c.c_void_p)]),
+    "shmem_ctx_get_team": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p)]),
 }
 
 _REDUCE_RE = re.compile(r"^shmem_(\w+?)_(and|or|xor|min|max|sum|prod)_(reduce|to_all)$")
@@ -181,7 +202,12 @@ _BY_VALUE = {"char": _c.c_char, "schar": _c.c_byte, "short": _c.c_short, "int": 
              "int32": _c.c_int32, "int64": _c.c_int64, "uint8": _c.c_uint8, "uint16": _c.c_uint16,
              "uint32": _c.c_uint32, "uint64": _c.c_uint64, "size": _c.c_size_t, "ptrdiff": _c.c_ssize_t,
              "float": _c.c_float, "double": _c.c_double, "longdouble": _c.c_longdouble}
+# the ctx twin of a typed call: shmem_ctx_<rest> / shmemx_ctx_<rest>, its plain form's arguments
+# behind a leading context handle
+_CTX_RE = re.compile(r"^(shmemx?)_ctx_(\w+)$")
+SHMEM_CTX_PRIVATE, SHMEM_CTX_SERIALIZED, SHMEM_CTX_NOSTORE = 1, 2, 4
 _declared = False
+_CTX_LIB = None
 
 
 def lib():
@@ -196,12 +222,26 @@ def lib():
     return L
 
 
+def ctx_lib():
+    """libsos_amd_ctx.so: the public shmem_ctx_* names.  It binds to whichever build of the
+    runtime lib() loaded (globally) before it."""
+    global _CTX_LIB
+    if _CTX_LIB is None:
+        lib()
+        _CTX_LIB = ctypes.CDLL(os.path.join(_lib.HERE, "libsos_amd_ctx.so"))
+    return _CTX_LIB
+
+
 def team_world():
     return ctypes.c_void_p.in_dll(lib(), "SHMEM_TEAM_WORLD").value
 
 
 def team_shared():
     return ctypes.c_void_p.in_dll(lib(), "SHMEM_TEAM_SHARED").value
+
+
+def ctx_default():
+    return ctypes.c_void_p.in_dll(lib(), "SHMEM_CTX_DEFAULT").value
 
 
 def team_node():
@@ -243,6 +283,17 @@ def __getattr__(name):
         return fn
     if name in _RUNTIME:
         return getattr(L, name)
+    if name in _CTX_RUNTIME:
+        fn = getattr(ctx_lib(), name)
+        fn.restype, fn.argtypes = _CTX_RUNTIME[name]
+        return fn
+    m = _CTX_RE.match(name)
+    if m:
+        fn = getattr(ctx_lib(), name)  # AttributeError where SOS has no ctx form (locks, waits, deprecated atomics)
+        plain = __getattr__(f"{m.group(1)}_{m.group(2)}")
+        fn.restype = plain.restype
+        fn.argtypes = [_c.c_void_p] + list(plain.argtypes)
+        return fn
     m = _PUT_SIGNAL_RE.match(name)
     if m and (m.group(1) is None or m.group(1) in _BY_VALUE):
         # (target, source, nelems, sig_addr, signal, sig_op, pe)
