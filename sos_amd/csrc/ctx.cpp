@@ -21,14 +21,14 @@
 //    nothing weaker is shown to order the copy engine's deliveries.
 //  * options are stored and returned; the library is not thread-multiple, so PRIVATE,
 //    SERIALIZED and NOSTORE change nothing else.
-//  * a handle is looked up, never dereferenced (sos_ctx_check, ctx_checks.cpp).
+//  * a handle is looked up, never dereferenced (sos_ctx_check, onesided_checks.cpp).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <algorithm>
 
-#include "api_internal.h"
+#include "onesided.h"
 #include "runtime.h"
 #include "sosx.h"
 

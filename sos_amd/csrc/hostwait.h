@@ -1,6 +1,7 @@
 // hostwait.h -- bounded host spins on words a peer PE or the GPU writes (p2p.cpp,
-// smallpath.cpp).  Internal to the library: kept out of its dynamic symbol table.
+// smallpath.cpp, signal.cpp, lock.cpp).  Internal to the library: kept out of its dynamic symbol table.
 #pragma once
+#include <sched.h>
 #include <stdlib.h>
 #include <time.h>
 
@@ -42,6 +43,22 @@ void spin_until(Ready ready, Idle idle, Expired expired)
         else if (t - t0 > wait_limit_s()) expired(t - t0);
     }
 }
+
+// The idle() of a wait that probes a word.  Device memory: a probe is a launch and its
+// completion, so look at the clock every time.  Memory the host addresses: a probe is a
+// load, so pause for 255 spins, then yield and look.
+struct ProbeCadence {
+    bool device;
+    bool operator()(unsigned spins) const
+    {
+        if (!device && (spins & 0xff)) {
+            __builtin_ia32_pause();
+            return false;
+        }
+        if (!device) sched_yield();
+        return true;
+    }
+};
 
 }  // namespace sosrt
 #pragma GCC visibility pop

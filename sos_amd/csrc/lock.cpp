@@ -26,7 +26,7 @@
 // SHMEMX_P2P_TIMEOUT seconds the job ends with sos_lock_expiry_message's text.
 //
 // Consumer half: after a successful acquire a peer's critical section has ended and its
-// bytes may have arrived: note_peer_wait and acquire_system, as a returning wait does.
+// bytes may have arrived: after_peer_wait (onesided.cpp), as a returning wait does.
 //
 // Where the lock is: with several PEs, the device symmetric heap (sos_lock_check); with
 // one PE any symmetric memory -- a kernel reaches the host heap and a registered data
@@ -38,14 +38,13 @@
 // PEs' heap bases are made at shmem_init and the table is refilled when the device heap is
 // mapped (lock_table_build); shmem_finalize releases both (lock_release).
 #include <hip/hip_runtime.h>
-#include <sched.h>
 #include <string.h>
 
 #include <vector>
 
-#include "api_internal.h"
 #include "hostwait.h"
 #include "lock_proto.h"
+#include "onesided.h"
 #include "runtime.h"
 #include "sosx.h"
 
@@ -55,8 +54,7 @@ using soslock::Result;
 namespace {
 
 struct LockState {
-    char *pinned = nullptr;      // [Result | probe word]
-    char *pinned_dev = nullptr;  // its device view
+    Pinned pinned;               // [Result | probe word]
     uint64_t *table = nullptr;   // device: every PE's heap base as mapped here
     std::vector<uint64_t> bases; // the host's copy
     long steps = 0, probes = 0;
@@ -127,10 +125,10 @@ Result step(int kind, const Where &w, long *lock, const char *fn)
         // stream's earlier work
         if (kind == SOSX_LOCK_RELEASE) hip_check(release_system(s.stream), fn);
         ++g.steps;
-        const int rc = sosx_lock_step(kind, w.last, w.data, g.table, w.offset, s.my_pe, s.n_pes, g.pinned_dev, s.stream);
+        const int rc = sosx_lock_step(kind, w.last, w.data, g.table, w.offset, s.my_pe, s.n_pes, g.pinned.dev, s.stream);
         if (rc != SOSX_OK) raise_error("%s: lock launch failed (%d)", fn, rc);
         hip_check(sync_system(s.stream), fn);
-        memcpy(&r, g.pinned, sizeof(r));
+        memcpy(&r, g.pinned.host, sizeof(r));
     }
     if (r.status == SOSX_LOCK_CORRUPT) corrupt(lock, r.bad, fn);
     return r;
@@ -143,11 +141,11 @@ uint32_t probe(const Where &w, const char *fn)
     ++g.probes;
     if (w.host) return __atomic_load_n(w.data, __ATOMIC_ACQUIRE);
     State &s = st();
-    const int rc = sosx_sync_snapshot(g.pinned_dev + kProbeOff, w.data, 1, sizeof(uint32_t), s.stream);
+    const int rc = sosx_sync_snapshot((char *)g.pinned.dev + kProbeOff, w.data, 1, sizeof(uint32_t), s.stream);
     if (rc != SOSX_OK) raise_error("%s: snapshot launch failed (%d)", fn, rc);
     hip_check(sync_system(s.stream), fn);
     uint32_t v;
-    memcpy(&v, g.pinned + kProbeOff, sizeof(v));
+    memcpy(&v, (char *)g.pinned.host + kProbeOff, sizeof(v));
     return v;
 }
 
@@ -155,42 +153,13 @@ uint32_t probe(const Where &w, const char *fn)
 uint32_t wait_for(const Where &w, uint32_t mask, uint32_t seen, int awaited, long *lock, const char *fn)
 {
     if (seen & mask) return seen;
-    const bool dev = !w.host;
-    spin_until([&] { return ((seen = probe(w, fn)) & mask) != 0; },
-               [dev](unsigned spins) {
-                   if (dev) return true;  // a probe is a launch and its completion: look every time
-                   if (spins & 0xff) {
-                       __builtin_ia32_pause();
-                       return false;
-                   }
-                   sched_yield();
-                   return true;
-               },
+    spin_until([&] { return ((seen = probe(w, fn)) & mask) != 0; }, ProbeCadence{!w.host},
                [&](double seconds) {
                    char msg[384];
                    sos_lock_expiry_message(fn, lock, awaited, seen, seconds, msg, sizeof(msg));
                    raise_error("%s", msg);
                });
     return seen;
-}
-
-// the consumer half of the hand-off (user_barrier's, runtime.cpp)
-void acquired(const char *fn)
-{
-    State &s = st();
-    if (s.n_pes > 1 && s.p2p_ready) {
-        note_peer_wait();
-        hip_check(acquire_system(s.stream), fn);
-    }
-}
-
-void checked(long *lock, const char *fn)
-{
-    RmaLayout lay;
-    rma_layout_now(lay);
-    const sos_lock_op op = {lock};
-    char msg[512];
-    if (sos_lock_check(&lay.l, &op, msg, sizeof(msg)) != SOS_RMA_OK) raise_error("%s: %s", fn, msg);
 }
 
 }  // namespace
@@ -202,10 +171,9 @@ void sosrt::lock_table_build()
 {
     State &s = st();
     LockState &g = lk();
-    if (!g.pinned) {
-        hip_check(hipHostMalloc((void **)&g.pinned, kPinnedBytes, hipHostMallocDefault), "hipHostMalloc(lock)");
-        hip_check(hipHostGetDevicePointer((void **)&g.pinned_dev, g.pinned, 0), "hipHostGetDevicePointer(lock)");
-        memset(g.pinned, 0, kPinnedBytes);
+    if (!g.pinned.host) {
+        g.pinned.reserve(kPinnedBytes, s.stream, "lock", "shmem_init");
+        memset(g.pinned.host, 0, kPinnedBytes);
     }
     if (!g.table) hip_check(hipMalloc((void **)&g.table, (size_t)s.n_pes * sizeof(uint64_t)), "hipMalloc(lock table)");
     g.bases.assign((size_t)s.n_pes, 0);
@@ -218,7 +186,7 @@ void sosrt::lock_table_build()
 void sosrt::lock_release()
 {
     LockState &g = lk();
-    if (g.pinned) (void)hipHostFree(g.pinned);
+    g.pinned.release();
     if (g.table) (void)hipFree(g.table);
     g = LockState();
 }
@@ -239,26 +207,26 @@ void sosx_lock_stats(long *steps, long *probes)
 
 void sos_api_set_lock(long *lock, const char *fn)
 {
-    checked(lock, fn);
+    checked(sos_lock_check, sos_lock_op{lock}, fn);
     const Where w = locate(lock, fn);
     const Result r = step(SOSX_LOCK_ENQUEUE, w, lock, fn);
     if (r.status == SOSX_LOCK_QUEUED) wait_for(w, soslock::kSignal, r.data, SOS_LOCK_AWAIT_SIGNAL, lock, fn);
-    acquired(fn);
+    after_peer_wait(st().stream, fn);  // the consumer half of the hand-off
 }
 
 int sos_api_test_lock(long *lock, const char *fn)
 {
-    checked(lock, fn);
+    checked(sos_lock_check, sos_lock_op{lock}, fn);
     const Where w = locate(lock, fn);
     const Result r = step(SOSX_LOCK_TRY, w, lock, fn);
     if (r.status != SOSX_LOCK_ACQUIRED) return 1;
-    acquired(fn);
+    after_peer_wait(st().stream, fn);  // the consumer half of the hand-off
     return 0;
 }
 
 void sos_api_clear_lock(long *lock, const char *fn)
 {
-    checked(lock, fn);
+    checked(sos_lock_check, sos_lock_op{lock}, fn);
     const Where w = locate(lock, fn);
     Result r = step(SOSX_LOCK_RELEASE, w, lock, fn);
     // a successor swapped `last` but has not linked itself yet: once NEXT is there, the

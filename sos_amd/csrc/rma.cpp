@@ -1,14 +1,11 @@
 // rma.cpp -- one-sided put / get on the device symmetric heap: the generic entries behind
 // shmem_put / get / p / g / iput / iget, shmemx_ibput / ibget and shmem_ptr (rma_gen.cpp).
 //
-// SOS's checks in SOS's order (src/data_c.c4:300-680) as one function of plain data
-// (sos_rma_check); the entries build its input from the runtime state, raise what it
-// refuses, translate the remote address and move the bytes on the library stream:
+// SOS's checks in SOS's order (src/data_c.c4:300-680) are one function of plain data
+// (sos_rma_check, onesided_checks.cpp); the entries raise what it refuses (checked),
+// translate the remote address (translate, onesided.cpp) and move the bytes on the library
+// stream:
 //
-//  * translation: a device-heap address belongs to PE `pe` at
-//    peer_heap[pe] + (addr - peer_heap[my_pe]) (every PE maps every heap under
-//    SHMEMX_TRANSPORT=p2p|both, ensure_device_heap); pe == my_pe needs no mapping and may
-//    name any symmetric memory;
 //  * contiguous forms: hipMemcpyAsync on the library stream behind a system-scope release
 //    (the copy engine reads HBM), as sosx_memcpy orders its copy; the blocking forms then
 //    complete the stream like every other call (sync_system);
@@ -20,195 +17,19 @@
 //    completion at once; the nbi forms only enqueue, and shmem_quiet / shmem_fence / every
 //    barrier and sync complete the stream with a system-scope release;
 //  * visibility, consumer half: a launch that reads a peer's heap follows an acquire
-//    issued after the last wait for a peer (acquire_system; note_peer_read counts it);
+//    issued after the last wait for a peer (before_peer_read, onesided.cpp);
 //  * contexts: "the library stream" above is the stream of the context the call names --
 //    SHMEM_CTX_DEFAULT for the plain forms -- with that context's release event, stage and
 //    acquire flag (ctx.cpp).
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include <string.h>
 
-#include <vector>
-
-#include "api_internal.h"
+#include "onesided.h"
 #include "runtime.h"
 #include "shmemx.h"
 #include "sosx.h"
 
 using namespace sosrt;
-
-extern "C" char __data_start[] __attribute__((weak));
-extern "C" char _end[] __attribute__((weak));
-
-// rma_find_region and rma_region_name live in signal_checks.cpp, the file without HIP
-
-namespace {
-
-// elements spanned by nblocks blocks of bsize at `stride` (>= 0); false if over size_t
-bool extent_bytes(size_t bsize, size_t nblocks, ptrdiff_t stride, size_t ts, size_t *out)
-{
-    const size_t s = stride > 0 ? (size_t)stride : 0;
-    if (s && nblocks - 1 > (SIZE_MAX / 32) / s) return false;
-    const size_t span = (nblocks - 1) * s;
-    if (bsize > SIZE_MAX / 32 - span) return false;
-    *out = (span + bsize) * ts;
-    return true;
-}
-
-}  // namespace
-
-extern "C" int sos_rma_check(const sos_rma_layout *l, const sos_rma_op *op, char *msg, size_t n)
-{
-#define REFUSE(code, ...)                \
-    do {                                 \
-        if (msg && n) snprintf(msg, n, __VA_ARGS__); \
-        return code;                     \
-    } while (0)
-    if (msg && n) msg[0] = 0;
-    const char *rname = op->put ? "target" : "source", *lname = op->put ? "source" : "target";
-    // the stride names as SOS's prototypes have them: tst is the target's
-    const char *rsname = op->put ? "tst" : "sst", *lsname = op->put ? "sst" : "tst";
-    if (!l->initialized) REFUSE(SOS_RMA_NOT_INITIALIZED, "library not initialized");
-    if (op->pe < 0 || op->pe >= l->n_pes) REFUSE(SOS_RMA_BAD_PE, "PE argument (%d) is invalid", op->pe);
-    const size_t ts = op->type_size;
-    if (ts != 1 && ts != 2 && ts != 4 && ts != 8 && ts != 16)
-        REFUSE(SOS_RMA_BAD_TYPE_SIZE, "element size %zu is not 1, 2, 4, 8 or 16", ts);
-    if (op->strided) {  // SHMEM_ERR_CHECK_POSITIVE(tst), then (sst)
-        const ptrdiff_t tst = op->put ? op->remote_stride : op->local_stride;
-        const ptrdiff_t sst = op->put ? op->local_stride : op->remote_stride;
-        if (tst <= 0) REFUSE(SOS_RMA_NOT_POSITIVE, "Argument %s must be positive (%ld)", "tst", (long)tst);
-        if (sst <= 0) REFUSE(SOS_RMA_NOT_POSITIVE, "Argument %s must be positive (%ld)", "sst", (long)sst);
-    }
-    const bool empty = op->bsize == 0 || op->nblocks == 0;
-    size_t rext = 0, lext = 0;
-    const sos_rma_region *reg = nullptr;
-    if (!empty) {
-        // SHMEM_ERR_CHECK_SYMMETRIC over the remote side's whole extent
-        const uintptr_t r = (uintptr_t)op->remote;
-        reg = rma_find_region(l, r);
-        if (!reg) REFUSE(SOS_RMA_NOT_SYMMETRIC, "Argument \"%s\" is not symmetric (%p)", rname, op->remote);
-        if (!extent_bytes(op->bsize, op->nblocks, op->remote_stride, ts, &rext) ||
-            rext > reg->size - (r - reg->base))
-            REFUSE(SOS_RMA_NOT_SYMMETRIC, "Argument \"%s\" [%p..%p) exceeds %s [%p..%p)", rname, op->remote,
-                   (const void *)(r + rext), rma_region_name(reg->kind), (const void *)reg->base,
-                   (const void *)(reg->base + reg->size));
-        // SHMEM_ERR_CHECK_NULL
-        if (!op->local) REFUSE(SOS_RMA_NULL_LOCAL, "Argument \"%s\" is NULL", lname);
-    }
-    // SHMEM_ERR_CHECK_STRIDE_GTE_BSIZE(tst), then (sst)
-    for (int k = 0; k < 2; ++k) {
-        const bool remote_first = op->put;  // tst first
-        const bool remote = (k == 0) == remote_first;
-        const ptrdiff_t s = remote ? op->remote_stride : op->local_stride;
-        if (s < 0 || (size_t)s < op->bsize)
-            REFUSE(SOS_RMA_STRIDE_LT_BSIZE, "Stride argument \"%s\" (%zd), is less than block size %zu",
-                   remote ? rsname : lsname, s, op->bsize);
-    }
-    if (empty) return SOS_RMA_OK;
-    if (!extent_bytes(op->bsize, op->nblocks, op->local_stride, ts, &lext))
-        REFUSE(SOS_RMA_NOT_SYMMETRIC, "Argument \"%s\": extent overflows size_t", lname);
-    if ((uintptr_t)op->remote % ts || (uintptr_t)op->local % ts)
-        REFUSE(SOS_RMA_BAD_TYPE_SIZE, "Arguments \"target\" (%p) and \"source\" (%p) must be aligned to the "
-               "element size %zu", op->put ? op->remote : op->local, op->put ? op->local : op->remote, ts);
-    if (op->pe == l->my_pe) {
-        // SHMEM_ERR_CHECK_OVERLAP, complete overlap not allowed
-        const char *a = (const char *)op->remote, *b = (const char *)op->local;
-        if (a < b + lext && b < a + rext) {
-            const char *lo = a < b ? a : b, *hi = a < b ? b : a;
-            REFUSE(SOS_RMA_OVERLAP, "Argument \"target\" [%p..%p) overlaps argument (%p)", (const void *)lo,
-                   (const void *)(lo + (lo == a ? rext : lext)), (const void *)hi);
-        }
-        return SOS_RMA_OK;
-    }
-    if (reg->kind != SOS_RMA_REGION_DEVICE_HEAP)
-        REFUSE(SOS_RMA_PEER_NOT_DEVICE_HEAP, "Argument \"%s\" (%p) is in this PE's %s: put/get to another PE "
-               "(%d) needs the device symmetric heap (shmemx_malloc_device), the only memory mapped across PEs",
-               rname, op->remote, rma_region_name(reg->kind), op->pe);
-    if (!l->mapped)
-        REFUSE(SOS_RMA_NO_PATH, "No path to peer (PE %d's device heap is not mapped: SHMEMX_TRANSPORT=p2p or "
-               "both maps it)", op->pe);
-    return SOS_RMA_OK;
-#undef REFUSE
-}
-
-namespace {
-
-bool heap_mapped(const State &s)
-{
-    if (!s.p2p_ready || s.peer_heap.size() != (size_t)s.n_pes) return false;
-    for (char *b : s.peer_heap)
-        if (!b) return false;
-    return true;
-}
-
-}  // namespace
-
-void sosrt::rma_layout_now(RmaLayout &out)
-{
-    State &s = st();
-    auto add = [&](const void *b, size_t n, int kind) {
-        if (b && n) out.regions.push_back({(uintptr_t)b, n, kind});
-    };
-    // the executable's data segment, as is_symmetric has it
-    const char *data = __data_start && _end ? __data_start : nullptr;
-    const size_t data_bytes = data ? (size_t)(_end - __data_start) : 0;
-    add(s.dev_heap.base, s.dev_heap.size, SOS_RMA_REGION_DEVICE_HEAP);
-    add(s.host_heap.base, s.host_heap.size, SOS_RMA_REGION_HOST_HEAP);
-    add(data, data_bytes, SOS_RMA_REGION_DATA);
-    for (auto &kv : s.dev_allocs) add(kv.first, kv.second, SOS_RMA_REGION_DEVICE_ALLOC);
-    out.l = {s.initialized && !s.finalized, s.my_pe, s.n_pes, heap_mapped(s), (int)out.regions.size(),
-             out.regions.data()};
-}
-
-namespace {
-
-void checked(const sos_rma_op &op, const char *fn)
-{
-    RmaLayout lay;
-    rma_layout_now(lay);
-    char msg[512];
-    if (sos_rma_check(&lay.l, &op, msg, sizeof(msg)) != SOS_RMA_OK) raise_error("%s: %s", fn, msg);
-}
-
-}  // namespace
-
-// the remote side's address on this PE
-char *sosrt::translate(const void *remote, int pe)
-{
-    State &s = st();
-    if (pe == s.my_pe) return (char *)remote;
-    return s.peer_heap[(size_t)pe] + ((const char *)remote - s.peer_heap[(size_t)s.my_pe]);
-}
-
-// Before a launch or copy that reads peer `pe`'s heap: the acquire a wait since the last
-// one left owed, and the read counted.
-void sosrt::before_peer_read(Ctx &c, int pe, const char *fn)
-{
-    if (pe == st().my_pe) return;
-    if (c.acq_pending) hip_check(acquire_system(c), fn);  // on the stream that does the read
-    note_peer_read(c, false);
-}
-
-// The address at which a kernel on this PE's GPU reaches the `bytes` bytes at p, or null
-// where it cannot (pageable host memory, or an extent only partly registered with HIP,
-// such as a data segment whose first page was rounded off).  Device memory is its own
-// address; host memory that HIP allocated or registered is reached through the device
-// pointer HIP reports for it (hipHostGetDevicePointer's), which need not equal p.
-char *sosrt::device_view(const void *p, size_t bytes)
-{
-    if (is_device_ptr(p)) return (char *)p;
-    hipPointerAttribute_t a, z;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess ||
-        hipPointerGetAttributes(&z, (const char *)p + bytes - 1) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    const bool host = a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
-    if (!host || z.type != a.type || !a.devicePointer || !z.devicePointer) return nullptr;
-    // one mapping over the whole extent
-    if ((char *)z.devicePointer - (char *)a.devicePointer != (ptrdiff_t)(bytes - 1)) return nullptr;
-    return (char *)a.devicePointer;
-}
 
 namespace {
 
@@ -276,7 +97,7 @@ void put_blocks(Ctx &c, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t
                 size_t ts, int pe, bool strided, const char *fn)
 {
     const sos_rma_op op = {dest, source, tst, sst, bsize, nblocks, ts, pe, 1, strided};
-    checked(op, fn);
+    checked(sos_rma_check, op, fn);
     if (!bsize || !nblocks) return;
     blocks(c, translate(dest, pe), tst, (const char *)source, sst, bsize, nblocks, ts, st().my_pe, fn);
 }
@@ -285,32 +106,27 @@ void get_blocks(Ctx &c, void *dest, const void *source, ptrdiff_t tst, ptrdiff_t
                 size_t ts, int pe, bool strided, const char *fn)
 {
     const sos_rma_op op = {source, dest, sst, tst, bsize, nblocks, ts, pe, 0, strided};
-    checked(op, fn);
+    checked(sos_rma_check, op, fn);
     if (!bsize || !nblocks) return;
     blocks(c, (char *)dest, tst, translate(source, pe), sst, bsize, nblocks, ts, pe, fn);
-}
-
-void put_on(Ctx &c, void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi, const char *fn)
-{
-    const sos_rma_op op = {dest, source, (ptrdiff_t)nelems, (ptrdiff_t)nelems, nelems, 1, type_size, pe, 1, 0};
-    checked(op, fn);
-    if (nelems) contiguous(c, translate(dest, pe), source, nelems * type_size, st().my_pe, nbi != 0, fn);
 }
 
 void get_on(Ctx &c, void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi, const char *fn)
 {
     const sos_rma_op op = {source, dest, (ptrdiff_t)nelems, (ptrdiff_t)nelems, nelems, 1, type_size, pe, 0, 0};
-    checked(op, fn);
+    checked(sos_rma_check, op, fn);
     if (nelems) contiguous(c, dest, translate(source, pe), nelems * type_size, pe, nbi != 0, fn);
 }
 
 }  // namespace
 
-// put on a context, for put-with-signal's composed form (signal.cpp)
+// put on a context: the entries below, and put-with-signal's composed form (signal.cpp)
 void sosrt::rma_put_on(Ctx &c, void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi,
                        const char *fn)
 {
-    put_on(c, dest, source, nelems, type_size, pe, nbi, fn);
+    const sos_rma_op op = {dest, source, (ptrdiff_t)nelems, (ptrdiff_t)nelems, nelems, 1, type_size, pe, 1, 0};
+    checked(sos_rma_check, op, fn);
+    if (nelems) contiguous(c, translate(dest, pe), source, nelems * type_size, st().my_pe, nbi != 0, fn);
 }
 
 // Every entry twice: on SHMEM_CTX_DEFAULT, and on the context the program names, whose
@@ -320,7 +136,7 @@ extern "C" {
 void sos_api_put(void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi,
                  const char *fn)
 {
-    put_on(default_ctx(), dest, source, nelems, type_size, pe, nbi, fn);
+    rma_put_on(default_ctx(), dest, source, nelems, type_size, pe, nbi, fn);
 }
 
 void sos_api_get(void *dest, const void *source, size_t nelems, size_t type_size, int pe, int nbi,
@@ -367,7 +183,7 @@ void sos_api_ctx_put(shmem_ctx_t ctx, void *dest, const void *source, size_t nel
                      int nbi, const char *fn)
 {
     Ctx &c = ctx_checked(ctx, &pe, fn);
-    put_on(c, dest, source, nelems, type_size, pe, nbi, fn);
+    rma_put_on(c, dest, source, nelems, type_size, pe, nbi, fn);
 }
 
 void sos_api_ctx_get(shmem_ctx_t ctx, void *dest, const void *source, size_t nelems, size_t type_size, int pe,

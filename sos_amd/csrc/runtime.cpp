@@ -18,6 +18,7 @@
 #include <string>
 
 #include "bootstrap.h"
+#include "onesided.h"
 #include "shmem.h"
 #include "shmemx.h"
 
@@ -680,11 +681,7 @@ void team_barrier(const Team &t)
 void user_barrier(const Team &t)
 {
     team_barrier(t);
-    State &s = st();
-    if (t.size > 1 && t.my_idx >= 0 && s.n_pes > 1 && s.p2p_ready) {
-        note_peer_wait();
-        hip_check(acquire_system(s.stream), "acquire after barrier");
-    }
+    if (t.size > 1 && t.my_idx >= 0) after_peer_wait(st().stream, "acquire after barrier");
 }
 
 Team *team_from_handle(shmem_team_t handle) { return reinterpret_cast<Team *>(handle); }

@@ -2,7 +2,7 @@
 // tests: the generic entries behind shmem_put_signal[_nbi], shmemx_signal_set / _add,
 // shmem_signal_fetch, shmem_signal_wait_until and shmem_<T>_wait_until* / _test*
 // (signal_gen.cpp).  Their checks and the comparison are plain functions of data
-// (signal_checks.cpp); the entries raise what those refuse.
+// (onesided_checks.cpp); the entries raise what those refuse (checked, onesided.cpp).
 //
 //  * put with signal is FUSED -- one launch of sosx_put_signal (putsignal.hip), which copies
 //    and then updates the signal word behind a system-scope release -- when target and
@@ -25,16 +25,15 @@
 //    seconds the job ends with a message naming the call, the ivar, the comparison, the
 //    wanted value and the last value seen.  test* runs exactly one probe.
 //  * consumer half: when a wait returns, or a test returns satisfied, a peer's bytes may
-//    have arrived: note_peer_wait and acquire_system, as user_barrier does after its
+//    have arrived: after_peer_wait (onesided.cpp), as user_barrier does after its
 //    rendezvous, so later launches on the stream read the payload fresh.
 #include <hip/hip_runtime.h>
-#include <sched.h>
 #include <string.h>
 
 #include <vector>
 
-#include "api_internal.h"
 #include "hostwait.h"
+#include "onesided.h"
 #include "runtime.h"
 #include "shmemx.h"
 #include "sosx.h"
@@ -51,9 +50,7 @@ constexpr size_t kFusedMaxDefault = 64u << 20;
 struct SignalState {
     size_t fused_max = kFusedMaxDefault;
     bool fused_read = false;
-    void *snap = nullptr;      // pinned host buffer of the probes
-    void *snap_dev = nullptr;  // its device view
-    size_t snap_bytes = 0;
+    Pinned snap;  // the probes' snapshot of the ivars
     long fused_calls = 0, composed_calls = 0, probes = 0;
 };
 
@@ -71,24 +68,6 @@ size_t fused_max()
         g.fused_read = true;
     }
     return g.fused_max;
-}
-
-void *snapshot_buffer(size_t bytes, const char *fn)
-{
-    SignalState &g = sig();
-    if (bytes <= g.snap_bytes) return g.snap;
-    if (g.snap) {
-        hip_check(sync_system(st().stream), fn);
-        (void)hipHostFree(g.snap);
-        g.snap = g.snap_dev = nullptr;
-        g.snap_bytes = 0;
-    }
-    size_t cap = 4096;
-    while (cap < bytes) cap *= 2;
-    hip_check(hipHostMalloc(&g.snap, cap, hipHostMallocDefault), "hipHostMalloc(sync snapshot)");
-    hip_check(hipHostGetDevicePointer(&g.snap_dev, g.snap, 0), "hipHostGetDevicePointer(sync snapshot)");
-    g.snap_bytes = cap;
-    return g.snap;
 }
 
 const char *cmp_name(int cmp)
@@ -130,24 +109,20 @@ struct Sync {
     const void *snap = nullptr;
     size_t index = SIZE_MAX, count = 0;
 
-    void setup(bool wait)
+    void setup()
     {
-        State &s = st();
-        RmaLayout lay;
-        rma_layout_now(lay);
-        const sos_sync_op op = {ivars, nelems, ts, status, indices, kind, cmp};
-        char msg[512];
-        if (sos_sync_check(&lay.l, &op, msg, sizeof(msg)) != SOS_RMA_OK) raise_error("%s: %s", fn, msg);
+        checked(sos_sync_check, sos_sync_op{ivars, nelems, ts, status, indices, kind, cmp}, fn);
         if (!nelems) return;
         device = is_device_ptr(ivars);
         if (device) {
-            snapshot_buffer(nelems * ts, fn);
+            size_t cap = 4096;  // in powers of two from a page
+            while (cap < nelems * ts) cap *= 2;
+            sig().snap.reserve(cap, st().stream, "sync snapshot", fn);
         } else {
             // what the stream still has queued (a signal or put of this PE to itself)
-            hip_check(sync_system(s.stream), fn);
+            hip_check(sync_system(st().stream), fn);
             host_words.resize((nelems * ts + 7) / 8);
         }
-        (void)wait;
     }
 
     // one probe: a fresh snapshot, compared
@@ -161,11 +136,11 @@ struct Sync {
         }
         if (device) {
             State &s = st();
-            SignalState &g = sig();
-            const int rc = sosx_sync_snapshot(g.snap_dev, ivars, nelems, ts, s.stream);
+            const Pinned &buf = sig().snap;
+            const int rc = sosx_sync_snapshot(buf.dev, ivars, nelems, ts, s.stream);
             if (rc != SOSX_OK) raise_error("%s: snapshot launch failed (%d)", fn, rc);
             hip_check(sync_system(s.stream), fn);
-            snap = g.snap;
+            snap = buf.host;
         } else {
             char *out = (char *)host_words.data();
             for (size_t i = 0; i < nelems; ++i) {
@@ -188,16 +163,6 @@ struct Sync {
         for (size_t i = 0; i < nelems; ++i)
             if (!status[i]) return false;
         return true;
-    }
-
-    // the consumer half of the hand-off (user_barrier's, runtime.cpp)
-    void acquire()
-    {
-        State &s = st();
-        if (s.n_pes > 1 && s.p2p_ready) {
-            note_peer_wait();
-            hip_check(acquire_system(s.stream), fn);
-        }
     }
 
     size_t result() const { return kind == SOS_SYNC_ANY ? index : kind == SOS_SYNC_SOME ? count : 0; }
@@ -234,13 +199,7 @@ void put_signal_on(Ctx &c, void *dest, const void *source, size_t nelems, size_t
                    uint64_t signal, int sig_op, int pe, int nbi, const char *fn)
 {
     State &s = st();
-    {
-        RmaLayout lay;
-        rma_layout_now(lay);
-        const sos_put_signal_op op = {dest, source, sig_addr, nelems, type_size, sig_op, pe};
-        char msg[512];
-        if (sos_put_signal_check(&lay.l, &op, msg, sizeof(msg)) != SOS_RMA_OK) raise_error("%s: %s", fn, msg);
-    }
+    checked(sos_put_signal_check, sos_put_signal_op{dest, source, sig_addr, nelems, type_size, sig_op, pe}, fn);
     const size_t bytes = nelems * type_size;
     const char *sdev = nullptr;
     const bool fused = bytes <= fused_max() && s.dev_heap.contains(sig_addr, sizeof(uint64_t)) &&
@@ -277,10 +236,7 @@ void signal_op_on(Ctx &c, uint64_t *sig_addr, uint64_t signal, int sig_op, int p
 
 void sosrt::signal_release()
 {
-    SignalState &g = sig();
-    if (g.snap) (void)hipHostFree(g.snap);
-    g.snap = g.snap_dev = nullptr;
-    g.snap_bytes = 0;
+    sig().snap.release();
     sosx_put_signal_release();
 }
 
@@ -336,21 +292,10 @@ size_t sos_api_wait(void *ivars, size_t nelems, size_t *indices, const int *stat
 {
     // the deprecated shmem_<T>_wait: until the ivar differs from value
     Sync w = {ivars, nelems, type_size, indices, status, cmp < 0 ? 2 : cmp, value, vector, kind, is_signed, fn};
-    w.setup(true);
+    w.setup();
     if (w.masked_out()) return w.result();  // SIZE_MAX for ANY, 0 otherwise: nothing to wait for
-    const bool dev = w.device;
-    spin_until([&] { return w.probe(); },
-               [dev](unsigned spins) {
-                   if (dev) return true;  // a probe is a launch and its completion: look every time
-                   if (spins & 0xff) {
-                       __builtin_ia32_pause();
-                       return false;
-                   }
-                   sched_yield();
-                   return true;
-               },
-               [&](double seconds) { w.expired(seconds); });
-    w.acquire();
+    spin_until([&] { return w.probe(); }, ProbeCadence{w.device}, [&](double seconds) { w.expired(seconds); });
+    after_peer_wait(st().stream, fn);  // the consumer half of the hand-off
     if (satisfied) *satisfied = as_unsigned(w.snap, 0, type_size);
     return w.result();
 }
@@ -359,10 +304,10 @@ size_t sos_api_test(void *ivars, size_t nelems, size_t *indices, const int *stat
                     int vector, int kind, size_t type_size, int is_signed, const char *fn)
 {
     Sync t = {ivars, nelems, type_size, indices, status, cmp, value, vector, kind, is_signed, fn};
-    t.setup(false);
+    t.setup();
     if (t.masked_out()) return kind == SOS_SYNC_ALL ? 1 : t.result();  // as SOS's loops leave it
     const bool ok = t.probe();
-    if (ok) t.acquire();
+    if (ok) after_peer_wait(st().stream, fn);
     if (kind == SOS_SYNC_ONE || kind == SOS_SYNC_ALL) return ok ? 1 : 0;
     return t.result();
 }

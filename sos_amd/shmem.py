@@ -103,14 +103,14 @@ _RUNTIME = {
                                            _c.c_size_t, _c.c_size_t, _c.c_void_p]),
     "sosx_block_copy_plan": (_c.c_int, [_c.c_void_p, _c.c_ssize_t, _c.c_void_p, _c.c_ssize_t, _c.c_size_t,
                                         _c.c_size_t, _c.c_size_t, _c.POINTER(_c.c_longlong)]),
-    # atomic memory operations: the generic entry, its checks and the kernel's C ABI (amo.cpp, amo.hip)
+    # atomic memory operations: the generic entry, its checks and the kernel's C ABI (amo.cpp, onesided_checks.cpp, amo.hip)
     "sos_api_amo": (None, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t,
                            _c.c_int, _c.c_int, _c.c_int, _c.c_char_p]),
     "sos_amo_check": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_char_p, _c.c_size_t]),
     "sosx_amo": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_size_t, _c.c_int,
                             _c.c_void_p]),
     # put with signal, signal operations, waits and tests: the generic entries, their checks, the
-    # comparison and the kernels' C ABI (signal.cpp, signal_checks.cpp, putsignal.hip)
+    # comparison and the kernels' C ABI (signal.cpp, onesided_checks.cpp, putsignal.hip)
     "sos_api_put_signal": (None, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p, _c.c_uint64,
                                   _c.c_int, _c.c_int, _c.c_int, _c.c_char_p]),
     "sos_api_signal_op": (None, [_c.c_void_p, _c.c_uint64, _c.c_int, _c.c_int, _c.c_char_p]),
@@ -137,7 +137,7 @@ _RUNTIME = {
     "shmem_wait": (None, [_c.c_void_p, _c.c_long]),
     "shmem_wait_until": (None, [_c.c_void_p, _c.c_int, _c.c_long]),
     # distributed locks: the three names, the generic entries, the check and message functions and the
-    # kernel's C ABI (lock.cpp, lock_checks.cpp, lock.hip)
+    # kernel's C ABI (lock.cpp, onesided_checks.cpp, lock.hip)
     "shmem_set_lock": (None, [_c.c_void_p]),
     "shmem_clear_lock": (None, [_c.c_void_p]),
     "shmem_test_lock": (_c.c_int, [_c.c_void_p]),
@@ -152,7 +152,7 @@ _RUNTIME = {
                                   _c.c_void_p, _c.c_void_p]),
     "sosx_lock_table": (_c.c_void_p, [_c.POINTER(_c.c_int)]),
     "sosx_lock_stats": (None, [_c.POINTER(_c.c_long), _c.POINTER(_c.c_long)]),
-    # communication contexts: the checks and the pool's size (ctx.cpp, ctx_checks.cpp); the public
+    # communication contexts: the checks and the pool's size (ctx.cpp, onesided_checks.cpp); the public
     # names are _CTX_RUNTIME's and __getattr__'s, from libsos_amd_ctx.so
     "sos_ctx_check": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.c_char_p,
                                  _c.c_size_t]),

@@ -1,5 +1,5 @@
 // ctx_checks_harness.cpp -- a program of its own over the plain check functions of the
-// communication contexts (sos_amd/csrc/ctx_checks.cpp, compiled next to it; no HIP, no
+// communication contexts (sos_amd/csrc/onesided_checks.cpp, compiled next to it; no HIP, no
 // library): the option mask, invalid / default / destroyed / unknown handles, the team-index
 // translation for a strided team, the SHMEMX_CTX_STREAMS values and the stream-pool
 // assignment.  Built plain and with the address and undefined-behaviour sanitizers

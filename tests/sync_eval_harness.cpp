@@ -1,5 +1,5 @@
 // sync_eval_harness.cpp -- a program of its own (no HIP, no Python) over the host-only
-// part of put-with-signal and the point-to-point waits (sos_amd/csrc/signal_checks.cpp,
+// part of put-with-signal and the point-to-point waits (sos_amd/csrc/onesided_checks.cpp,
 // compiled into it): sos_sync_eval against a model written from SOS's loops
 // (src/synchronization_c.c4), sos_put_signal_check and sos_sync_check over hand-built
 // layouts, and the copy split of sosx_put_signal (putsignal_plan.h) walked as the kernel's

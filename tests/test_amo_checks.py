@@ -1,4 +1,4 @@
-"""CPU: the argument checks of the atomic entries (sos_amo_check, amo.cpp) as a plain
+"""CPU: the argument checks of the atomic entries (sos_amo_check, onesided_checks.cpp) as a plain
 function over a made-up layout: each refusal returns its code and its message, in SOS's
 order (src/atomic_c.c4: initialized, PE, symmetric over sizeof(TYPE)), and the kernel's C
 ABI (sosx_amo) refuses bad arguments before any device work.  Nothing is started that

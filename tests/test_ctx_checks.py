@@ -1,13 +1,14 @@
-"""CPU: the checks of the communication contexts (sos_amd/csrc/ctx_checks.cpp) as plain
+"""CPU: the checks of the communication contexts (sos_amd/csrc/onesided_checks.cpp) as plain
 functions of data.
 
-(a) tests/ctx_checks_harness.cpp, a program of its own compiled with ctx_checks.cpp -- no HIP,
+(a) tests/ctx_checks_harness.cpp, a program of its own compiled with onesided_checks.cpp -- no HIP,
     no library -- plain and with -fsanitize=address,undefined: the option mask; invalid,
     default, destroyed and unknown handles, looked up and never dereferenced (the handles are
     made-up numbers); the team-index translation for the strided team start 1, stride 2,
     size 3 of 8 PEs (0, 1, 2 -> PEs 1, 3, 5; 3 refused with put / get's bad-PE message); the
     SHMEMX_CTX_STREAMS values; the stream-pool assignment for pools of 1, 3 and 31.
-(b) the same functions through the library's exports, and that the file has no HIP in it.
+(b) the same functions through the library's exports, and that the file -- which holds every
+    check of the one-sided layer -- has no HIP in it.
 Nothing is started that could abort."""
 import ctypes
 import os
@@ -31,7 +32,7 @@ def harness(request):
     exe = os.path.join(OUT, f"ctx_checks_harness_{request.param}")
     cmd = ["g++", "-std=c++17", "-Wall", "-Werror", *FLAVOURS[request.param], "-I" + CSRC,
            "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "ctx_checks_harness.cpp"),
-           os.path.join(CSRC, "ctx_checks.cpp"), "-o", exe]
+           os.path.join(CSRC, "onesided_checks.cpp"), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     return exe
@@ -47,8 +48,8 @@ def test_harness_passes(harness):
 
 
 def test_file_has_no_hip():
-    text = open(os.path.join(CSRC, "ctx_checks.cpp")).read()
-    code = text.split('#include "api_internal.h"')[1]
+    text = open(os.path.join(CSRC, "onesided_checks.cpp")).read()
+    code = text.split('#include "onesided_checks.h"')[1]
     assert "#include <hip" not in text and "hip" not in code and "runtime.h" not in text
 
 

@@ -1,4 +1,4 @@
-"""CPU: the argument check of the distributed locks (sos_lock_check, lock_checks.cpp) as a plain
+"""CPU: the argument check of the distributed locks (sos_lock_check, onesided_checks.cpp) as a plain
 function over a made-up layout: every refusal returns its code and a message naming the
 argument, in SOS's order (src/lock_c.c:44-65: initialized, `lock` symmetric over
 sizeof(long)) followed by this library's own (alignment; beyond one PE the device heap, then

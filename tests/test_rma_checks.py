@@ -1,4 +1,4 @@
-"""CPU: the argument checks of the one-sided entries (sos_rma_check, rma.cpp) as a plain
+"""CPU: the argument checks of the one-sided entries (sos_rma_check, onesided_checks.cpp) as a plain
 function: each refusal returns its code and its message, in SOS's order
 (src/data_c.c4:300-680), and nothing is started that could abort."""
 import ctypes

@@ -1,5 +1,5 @@
 """CPU: the argument checks of put-with-signal and of the waits and tests
-(sos_put_signal_check, sos_sync_check, signal_checks.cpp) as plain functions over a made-up
+(sos_put_signal_check, sos_sync_check, onesided_checks.cpp) as plain functions over a made-up
 layout: every refusal returns its code and a message naming the argument, in SOS's order
 (src/data_c.c4:691-699: initialized, PE, target symmetric, source NULL, overlap for
 pe == my_pe, sig_op; src/synchronization_c.c4: initialized, ivars symmetric, the overlaps,

@@ -1,4 +1,4 @@
-"""CPU: sos_sync_eval (signal_checks.cpp), the comparison of a wait or test over a snapshot
+"""CPU: sos_sync_eval (onesided_checks.cpp), the comparison of a wait or test over a snapshot
 of its ivars, against a short Python model written from SOS's macros (SHMEM_TEST and the
 loops of src/synchronization_c.c4): all six comparisons x widths 2 / 4 / 8 x signed /
 unsigned with values at the sign boundary, status NULL / all-masked / partly masked, nelems

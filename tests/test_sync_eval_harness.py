@@ -1,6 +1,6 @@
 """CPU: the host-only part of put-with-signal and the point-to-point waits as a program of
 its own.  tests/sync_eval_harness.cpp (its own main; compiled together with
-sos_amd/csrc/signal_checks.cpp, no HIP, no Python process, nothing preloaded) sweeps
+sos_amd/csrc/onesided_checks.cpp, no HIP, no Python process, nothing preloaded) sweeps
 sos_sync_eval against a model of SOS's loops, both check functions over hand-built layouts and
 the copy split of sosx_put_signal; it runs plain and under AddressSanitizer + UBSan, with
 buffers of the exact extents."""
@@ -11,7 +11,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = [os.path.join(ROOT, "tests", "sync_eval_harness.cpp"), os.path.join(ROOT, "sos_amd", "csrc", "signal_checks.cpp")]
+SRCS = [os.path.join(ROOT, "tests", "sync_eval_harness.cpp"), os.path.join(ROOT, "sos_amd", "csrc", "onesided_checks.cpp")]
 INCLUDES = [f"-I{ROOT}/include", f"-I{ROOT}/sos_amd/csrc"]
 
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
