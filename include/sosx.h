@@ -340,6 +340,18 @@ int sosx_gather_signalled(int nseg, const void *const *srcs, void *const *dsts,
                           const size_t *bytes, int nw, uint64_t *const *waddr,
                           const uint64_t *wval, int nq, const uint64_t *const *qaddr,
                           const uint64_t *qval, uint64_t *err, long long limit_ticks, void *stream);
+/* The launches that call (gated != 0) or sosx_gather (gated == 0) would make
+ * (sos_amd/csrc/gather_plan.h): out = copy launches, total tiles, live (non-empty)
+ * segments, segment slots packed over all launches (== live: each segment is copied by
+ * exactly one launch), gate placement (0 no gate, 1 fused into the copy launch, 2 its own
+ * step before the copies, 3 its own step with nothing copied), the first and the last
+ * launch's workgroups, 0.  Host only; the addresses are not dereferenced. */
+int sosx_gather_plan(int nseg, const uintptr_t *srcs, const uintptr_t *dsts, const size_t *bytes,
+                     int gated, long long out[8]);
+/* `seconds` in ticks of `device`'s wall clock, the unit of limit_ticks (the conversion the
+ * p2p transport applies to SHMEMX_P2P_TIMEOUT); 0 when the device does not report its
+ * rate. */
+long long sosx_p2p_ticks(int device, double seconds);
 
 /* The p2p transport's signalling mode: 1 = stream-ordered device signals, 0 = host
  * synchronisation every round (SHMEMX_P2P_SIGNAL=host), -1 = no p2p transport. */

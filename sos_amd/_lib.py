@@ -116,6 +116,16 @@ _SIGS = {
     "sosx_acquire_system": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     "sosx_gather": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
                                _c.POINTER(_c.c_size_t), _c.c_void_p]),
+    "sosx_gather_signalled": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
+                                         _c.POINTER(_c.c_size_t), _c.c_int, _c.POINTER(_c.c_void_p),
+                                         _c.POINTER(_c.c_uint64), _c.c_int, _c.POINTER(_c.c_void_p),
+                                         _c.POINTER(_c.c_uint64), _c.c_void_p, _c.c_longlong, _c.c_void_p]),
+    "sosx_gather_plan": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t),
+                                    _c.POINTER(_c.c_size_t), _c.c_int, _c.POINTER(_c.c_longlong)]),
+    "sosx_p2p_signal": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_uint64), _c.c_int,
+                                   _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_uint64), _c.c_void_p,
+                                   _c.c_longlong, _c.c_void_p]),
+    "sosx_p2p_ticks": (_c.c_longlong, [_c.c_int, _c.c_double]),
     "sosx_strided_copy": (_c.c_int, [_c.c_void_p, _c.c_ssize_t, _c.c_void_p, _c.c_ssize_t, _c.c_size_t,
                                      _c.c_size_t, _c.c_void_p]),
     "sosx_plan_extents": (_c.c_int, [_c.c_int, _c.c_int, _c.c_ulonglong, _c.c_ulonglong,
@@ -247,6 +257,21 @@ def block_strided_copy(dst_ptr, dst_stride, src_ptr, src_stride, bsize, nblocks,
                   ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
     return check(f(dst_ptr, dst_stride, src_ptr, src_stride, bsize, nblocks, elem_size, stream),
                  "sosx_block_strided_copy")
+
+
+def gather_plan(srcs, dsts, sizes, gated=False):
+    """The launches sosx_gather (or, gated, sosx_gather_signalled) would make for the
+    segments (srcs[i], dsts[i], sizes[i]) given as addresses: a dict of copy launches,
+    total tiles, live segments, segment slots packed over all launches, gate placement (0
+    none, 1 fused, 2 own step before the copies, 3 own step alone) and the first and the
+    last launch's workgroups (sosx_gather_plan; host only)."""
+    n = len(sizes)
+    arr = ctypes.c_size_t * max(n, 1)
+    out = (ctypes.c_longlong * 8)()
+    check(lib().sosx_gather_plan(n, arr(*srcs), arr(*dsts), arr(*sizes), 1 if gated else 0, out),
+          "sosx_gather_plan")
+    keys = ("launches", "tiles", "live", "slots", "gate", "first_blocks", "last_blocks")
+    return dict(zip(keys, list(out)))
 
 
 def plan_extents(alg, P, count, ts):

@@ -7,14 +7,11 @@
 // would use one link at a time.  16-B nontemporal loads/stores on the 16-B congruent
 // body of each segment, bytes for the ragged ends.
 #include "elementwise.h"
-
-#ifndef GATHER_U
-#define GATHER_U 4
-#endif
+#include "gather_plan.h"
 
 namespace sos {
 
-constexpr int kMaxSeg = 16;
+static_assert(kGatherThreads == (unsigned)kThreads, "gather_plan.h tiles by the workgroup size");
 
 // ---------------------------------------------------------------------------------
 // Stream-ordered signalling of the peer-to-peer transport (p2p.cpp): one lane per
@@ -110,14 +107,12 @@ struct GatherArgs {
 // of at most 16 workgroups (<= 256 KiB): waiting workgroups hold their CUs, and with
 // several PEs on one GPU 256-workgroup gates starved the peers' kernels (a 4 MiB ring
 // call at P = 2 took 67 us instead of 30, profiles/r2_p2p_signal_latency.txt).
-constexpr int kMaxGate = 16;
-constexpr unsigned kGateMaxBlocks = 16;
+constexpr int kMaxGate = 16;  // kGateMaxBlocks: gather_plan.h
 
 // One tile of kGatherU 16-B vectors per lane, one tile per workgroup (the combine's
 // shape: every load of the tile issued before the first store, no grid-stride loop);
-// a tile lies in one segment, so the segment lookup is uniform per workgroup.
-constexpr int kGatherU = GATHER_U;
-constexpr uint64_t kTileVec = (uint64_t)kThreads * kGatherU;
+// a tile lies in one segment, so the segment lookup is uniform per workgroup
+// (kGatherU, kTileVec: gather_plan.h).
 
 template <bool GATED>
 __global__ __launch_bounds__(kThreads) void k_gather(GatherArgs g, Sig<kMaxGate> gate)
@@ -236,14 +231,15 @@ int launch_step(const Sig<kMaxGate> &gate, hipStream_t st)
     return hip_ok(hipGetLastError());
 }
 
-// Copy nseg (src, dst, bytes) segments, <= 16 per launch.  `gate` (or null): a
-// signalling step that must precede the copies.  It rides in the copy launch when the
-// whole gather is ONE launch of at most kGateMaxBlocks tiles (each workgroup acquires
-// after its own wait); otherwise it runs as its own k_p2p_signal launch and -- when it
-// awaits posts -- the copies owe the acquire (carry_acquire: in their workgroups, or the
-// acquire kernel first), so every copy launch reads the peers' bytes behind a
-// system-scope acquire.  The copies' sources are peer memory
-// whenever the transport asked for an acquire.
+// Copy nseg (src, dst, bytes) segments, <= 16 per launch, every launch built from
+// gather_plan.h (each live segment in exactly one).  `gate` (or null): a signalling step
+// that must precede the copies.  It rides in the copy launch when the whole gather is ONE
+// launch of at most kGateMaxBlocks tiles (each workgroup acquires after its own wait);
+// otherwise it runs as its own k_p2p_signal launch and -- when it awaits posts -- the
+// copies owe the acquire (carry_acquire: in their workgroups, or the acquire kernel
+// first), so every copy launch reads the peers' bytes behind a system-scope acquire
+// (DESIGN.md section 7.3).  The copies' sources are peer memory whenever the transport
+// asked for an acquire.
 int gather_impl(int nseg, const void *const *srcs, void *const *dsts, const size_t *bytes,
                 const Sig<kMaxGate> *gate, hipStream_t st)
 {
@@ -254,63 +250,48 @@ int gather_impl(int nseg, const void *const *srcs, void *const *dsts, const size
         bool peer;
         ~Restore() { c.peer = peer; }
     } restore{c, peer_was};
-    bool gate_pending = gate != nullptr;
-    int live = 0;
-    for (int i = 0; i < nseg; ++i) live += bytes[i] != 0;
-    const bool one_launch = live <= kMaxSeg;
-    for (int base = 0; base < nseg; base += kMaxSeg) {
+    GatherCursor cur = gather_begin(nseg, bytes, gate != nullptr);
+    GatherLaunch l;
+    int more;
+    while ((more = gather_next(&cur, &l, nseg, srcs, dsts, bytes, gather_realign_mode() == 2)) == 1) {
         GatherArgs g;
         memset(&g, 0, sizeof(g));
-        int n = 0;
-        uint64_t tot = 0;
-        for (int i = base; i < nseg && n < kMaxSeg; ++i) {
-            if (!bytes[i]) continue;
-            const uintptr_t s = (uintptr_t)srcs[i], d = (uintptr_t)dsts[i];
-            g.src[n] = (const char *)srcs[i];
-            g.dst[n] = (char *)dsts[i];
-            g.bytes[n] = bytes[i];
-            // the body on dst's 16-B grid; an incongruent src is realigned in registers
-            // (every load is a 16-B-aligned block holding at least one byte of the
-            // segment, so none crosses a page the segment does not touch)
-            uint64_t h = (16 - (d & 15)) & 15;
-            if (h > bytes[i]) h = bytes[i];
-            g.head[n] = h;
-            g.nvec[n] = (bytes[i] - h) / 16;
-            g.sd[n] = (unsigned)((s + h) & 15);
-            g.tstart[n] = tot;
-            tot += (g.nvec[n] + kTileVec - 1) / kTileVec;
-            ++n;
+        for (int n = 0; n < l.nseg; ++n) {
+            g.src[n] = (const char *)srcs[l.seg[n]];
+            g.dst[n] = (char *)dsts[l.seg[n]];
+            g.head[n] = l.head[n];
+            g.sd[n] = l.sd[n];
+            g.nvec[n] = l.nvec[n];
+            g.bytes[n] = l.bytes[n];
+            g.tstart[n] = l.tstart[n];
         }
-        if (!n) continue;
-        g.nseg = n;
-        g.tstart[n] = tot;
-        g.ul = gather_realign_mode() == 2;
-        const uint64_t blocks = tot ? tot : 1;  // one tile per workgroup (+ the ragged ends)
-        if (blocks > 0xffffffffull) return SOSX_ERR_ARG;
-        Sig<kMaxGate> none;
-        memset(&none, 0, sizeof(none));
-        if (gate_pending && one_launch && blocks <= kGateMaxBlocks) {
-            g.acquire = carry_acquire(st, (unsigned)blocks);
+        g.tstart[l.nseg] = l.tstart[l.nseg];
+        g.nseg = l.nseg;
+        g.ul = l.ul;
+        const unsigned blocks = (unsigned)l.blocks;
+        if (l.gate == GG_FUSED) {
+            g.acquire = carry_acquire(st, blocks);
             if (g.acquire < 0) return SOSX_ERR_HIP;
-            hipLaunchKernelGGL(k_gather<true>, dim3((unsigned)blocks), dim3(kThreads), 0, st, g, *gate);
+            hipLaunchKernelGGL(k_gather<true>, dim3(blocks), dim3(kThreads), 0, st, g, *gate);
             if (gate->nq > 0 && !g.acquire) ++c.carried;  // acquired after the step's own wait
-            gate_pending = false;
         } else {
-            if (gate_pending) {  // large or several grids: the step as its own launch
+            if (l.gate == GG_STEP_BEFORE) {  // large or several grids: the step as its own launch
                 if (launch_step(*gate, st) != SOSX_OK) return SOSX_ERR_HIP;
                 if (gate->nq > 0) {  // it awaited posts: the copies owe the acquire
                     c.want = true;
                     c.peer = true;
                 }
-                gate_pending = false;
             }
-            g.acquire = carry_acquire(st, (unsigned)blocks);
+            Sig<kMaxGate> none;
+            memset(&none, 0, sizeof(none));
+            g.acquire = carry_acquire(st, blocks);
             if (g.acquire < 0) return SOSX_ERR_HIP;
-            hipLaunchKernelGGL(k_gather<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, g, none);
+            hipLaunchKernelGGL(k_gather<false>, dim3(blocks), dim3(kThreads), 0, st, g, none);
         }
         if (hipGetLastError() != hipSuccess) return SOSX_ERR_HIP;
     }
-    if (gate_pending && launch_step(*gate, st) != SOSX_OK) return SOSX_ERR_HIP;  // nothing copied
+    if (more != 0) return SOSX_ERR_ARG;
+    if (cur.gate_pending && launch_step(*gate, st) != SOSX_OK) return SOSX_ERR_HIP;  // nothing copied
     return SOSX_OK;
 }
 
@@ -372,6 +353,28 @@ int sosx_gather_signalled(int nseg, const void *const *srcs, void *const *dsts,
     gate.err = err;
     gate.limit = limit_ticks;
     return gather_impl(nseg, srcs, dsts, bytes, &gate, as_stream(stream));
+}
+
+// The launches that call would make (gather_plan.h), without touching a device: out =
+// launches, total tiles, live segments, segment slots over all launches, gate placement
+// (0 none, 1 fused, 2 own step before the copies, 3 own step with nothing copied), the
+// first and the last launch's grid, 0.
+int sosx_gather_plan(int nseg, const uintptr_t *srcs, const uintptr_t *dsts, const size_t *bytes, int gated,
+                     long long out[8])
+{
+    if (nseg < 0 || !out || (nseg && (!srcs || !dsts || !bytes))) return SOSX_ERR_ARG;
+    GatherSummary s;
+    if (gather_summary(&s, nseg, srcs, dsts, bytes, gated != 0, gather_realign_mode() == 2) != 0)
+        return SOSX_ERR_ARG;
+    out[0] = s.launches;
+    out[1] = s.tiles;
+    out[2] = s.live;
+    out[3] = s.slots;
+    out[4] = s.gate;
+    out[5] = s.first_blocks;
+    out[6] = s.last_blocks;
+    out[7] = 0;
+    return SOSX_OK;
 }
 
 // A system-scope acquire in stream order (k_acquire_system above); xcc_mask: a device word

@@ -253,12 +253,8 @@ void p2p_signal_setup()
     } else {
         ok = 0;
     }
-    int rate_khz = 0;
-    if (ok && (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, s.device) != hipSuccess ||
-               rate_khz <= 0)) {
-        (void)hipGetLastError();
-        ok = 0;
-    }
+    const long long ticks_per_s = ok ? sosx_p2p_ticks(s.device, 1.0) : 0;
+    if (ticks_per_s <= 0) ok = 0;  // no wall-clock rate: the device waits could not be bounded
     // which GPU this PE drives (PCI bus id): stream mode is the default only when every
     // PE shares one device -- the configuration every stream-mode measurement and test
     // ran in.  Across GPUs the device-side flags cross xGMI through host memory, which
@@ -281,7 +277,7 @@ void p2p_signal_setup()
     }
     g_sig.capable = ok != 0;
     g_sig.dbase = (char *)dptr;
-    g_sig.limit_ticks = (long long)(wait_limit_s() * 1e3 * (double)rate_khz);
+    g_sig.limit_ticks = (long long)(wait_limit_s() * (double)ticks_per_s);
     // SHMEMX_P2P_SIGNAL = stream | host (the same on every PE: job environment); unset:
     // stream on one device, host across devices
     const char *e = getenv("SHMEMX_P2P_SIGNAL");
@@ -307,6 +303,18 @@ bool p2p_stream_capable() { return g_sig.capable; }
 void p2p_set_stream_signalling(bool on) { g_sig.on = on && g_sig.capable; }
 
 }  // namespace sosrt
+
+// `seconds` in ticks of `device`'s wall clock, the unit of the device waits' limit
+// (wall_clock64 in copy.hip's sig_step counts them); 0 when the device reports no rate.
+extern "C" long long sosx_p2p_ticks(int device, double seconds)
+{
+    int rate_khz = 0;
+    if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || rate_khz <= 0) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return (long long)(seconds * 1e3 * (double)rate_khz);
+}
 
 // 1 = stream-ordered device signals, 0 = host synchronisation, -1 = no p2p transport
 extern "C" int sosx_p2p_signal_mode(void)

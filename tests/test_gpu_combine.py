@@ -242,6 +242,17 @@ def test_fill_matches_oracle(torch_cuda, sos, oracle):
             sos.fill(dt, dist, 1234, 3, buf.data_ptr(), n, 77)
             torch.cuda.synchronize()
             assert same_bits(from_dev(buf, 0, ref), ref), (dt, dist)
+            # the same elements generated as two calls that meet inside a workgroup, behind
+            # guard bytes: index0 shifts the stream and nothing past the count is written
+            cut = 4999
+            buf2 = torch.full((ref.nbytes + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+            sos.fill(dt, dist, 1234, 3, buf2.data_ptr(), cut, 77)
+            sos.fill(dt, dist, 1234, 3, buf2.data_ptr() + cut * ref.itemsize, n - cut, 77 + cut)
+            torch.cuda.synchronize()
+            assert same_bits(from_dev(buf2, 0, ref), ref), (dt, dist, "two calls")
+            assert bool((buf2[ref.nbytes:] == 0xA5).all()), (dt, dist)
+    # tests/test_gpu_checkers.py: every kind of the kernel's switch, index0 past 2^32, the
+    # grid cap and the status codes
 
 
 # ---------------------------------------------------------------------------------
